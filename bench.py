@@ -35,9 +35,26 @@ against the chosen update_halo_ schedule over 24 steps and A/B-timed too.
 Every host wait on the GPU is bounded (IGG_COMM_TIMEOUT): a rank whose peer
 died aborts RCCL and fails instead of hanging.
 
+A plain run does what the headline figure needs and no more: set-up (the
+stencil autotune and, at N > 1, the choice of the exchange the steps use),
+warm-up, the K timed steps, the result line. ``--full`` adds everything
+else, as it ran by default before: the same-job efficiency
+(``config.efficiency``), the post-timing checks (fused exchange and timed
+transport at N > 1, the second-stencil-variant replay at any N; a failed
+check re-times or yields no number), the stencil/halo phase split and the
+blocking gather timings.
+
+``--dump-outputs DIR`` writes the fields the last timed step left (diffusion:
+T; acoustic: P, Vx, Vy) as ``DIR/<name>.npy`` (ranks > 0:
+``<name>.rank<r>.npy``) in the run's dtype, at most DUMP_MAX_BYTES in all: a
+larger field as a fixed seeded sample of its flattened entries. Such a run
+warms up for a fixed number of steps (DUMP_WARM_STEPS), so with the same
+arguments the same steps run from the same initial fields every time.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512]
                        [--dtype float64] [--overlap] [--variant V|auto]
                        [--transport auto|rccl|put] [--no-graph] [--device gpu|cpu]
+                       [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -171,6 +188,12 @@ def parse():
                     help="cpu: host fields and the gloo exchange (launch/plumbing check, no GPU needed)")
     ap.add_argument("--launch-timeout", type=float, default=1800.0,
                     help="self-launch: seconds before the ranks are stopped and the run fails")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the same-job efficiency, the post-timing "
+                         "checks (fused exchange, transport, second stencil variant), the phase split and the "
+                         "blocking gather timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fields the last timed step left as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -1223,6 +1246,55 @@ def validate_host_matching(field, comm, log) -> dict:
     return res
 
 
+# --dump-outputs: the arrays of one run hold at most DUMP_MAX_BYTES in all
+# (half of the 64 MB a dump may take, .npy headers included); a field above its
+# share is written as a fixed sample of its entries (the same DUMP_SEED-drawn
+# flat indices in every run, in ascending order).
+DUMP_MAX_BYTES = 32 * 1000 * 1000
+DUMP_SEED = 20240229
+# Untimed warm-load steps of a --dump-outputs run: a fixed count instead of the
+# measured IGG_BENCH_WARM_MS worth of steps, so the state the timed steps start
+# from - and with it every dumped value - is the same from run to run and from
+# build to build (200 steps: 56 ms of the fastest config, acoustic2d).
+DUMP_WARM_STEPS = 200
+
+
+def _outputs(model) -> list[str]:
+    """Names of the fields a caller of the time loop reads after its last step."""
+    return ["P", "Vx", "Vy"] if hasattr(model, "Vx") else ["T"]
+
+
+def _take_outputs(model, nprocs: int) -> dict:
+    """Host copies of this rank's output fields as the last step left them
+    (fused diffusion steps: halo planes materialised first, as before a
+    gather_; collective), whole or - above this rank's share of
+    DUMP_MAX_BYTES - as the fixed 1-D sample."""
+    import torch
+
+    if getattr(model, "fused", False) and hasattr(model, "sync_halo"):
+        model.sync_halo()
+    names = _outputs(model)
+    share = DUMP_MAX_BYTES // (len(names) * nprocs)
+    out = {}
+    for nm in names:
+        t = getattr(model, nm)
+        k = share // t.element_size()
+        if t.numel() > k:
+            idx = torch.randint(t.numel(), (k,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            t = t.view(-1)[idx.to(t.device)]
+        out[nm] = t.to("cpu", copy=True)
+    return out
+
+
+def _write_outputs(dirname: str, outs: dict, me: int) -> None:
+    """``DIR/<name>.npy`` (rank 0) / ``DIR/<name>.rank<r>.npy`` (other ranks)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for nm, t in outs.items():
+        np.save(os.path.join(dirname, f"{nm}.npy" if me == 0 else f"{nm}.rank{me}.npy"), t.numpy())
+
+
 T_START = time.monotonic()
 
 
@@ -1355,7 +1427,7 @@ def main():
     # and processes. Before the snapshot and the warm load below (it ends with
     # one halo exchange: the local steps leave the halos unexchanged).
     eff = None
-    if os.environ.get("IGG_BENCH_EFFICIENCY", "1") != "0":
+    if args.full and os.environ.get("IGG_BENCH_EFFICIENCY", "1") != "0":
         PH.enter("efficiency", _path_key(model), deadline=300)
         eff = measure_efficiency(model, comm, log, graph_ok, args.steps)
         ORDER.append("efficiency")
@@ -1378,7 +1450,7 @@ def main():
         IGG_BENCH_WARM_MS (default 40 ms) right before the timed region,
         which is unchanged: exactly K full steps."""
         PH.enter("warmup", _path_key(model), deadline=300)
-        if not getattr(model, "fused", False):
+        if args.full and not getattr(model, "fused", False):
             _save_start(model, pre)
         else:
             pre.clear()
@@ -1386,10 +1458,13 @@ def main():
         warm_ms = float(os.environ.get("IGG_BENCH_WARM_MS", "40"))
         if on_gpu and warm_ms > 0:
             if warm["extra"] is None:
-                est, k_est = _step_estimate_ms(model, comm)
-                since += k_est
                 k = max(1, getattr(model, "graph_steps", 1) if getattr(model, "graph", None) is not None else 1)
-                warm["extra"] = int(-(-warm_ms // (est * k))) * k
+                if args.dump_outputs:
+                    warm["extra"] = -(-DUMP_WARM_STEPS // k) * k  # a fixed count: see DUMP_WARM_STEPS
+                else:
+                    est, k_est = _step_estimate_ms(model, comm)
+                    since += k_est
+                    warm["extra"] = int(-(-warm_ms // (est * k))) * k
             model.run(warm["extra"])
             since += warm["extra"]
         warm["since_snapshot"] = since
@@ -1432,14 +1507,20 @@ def main():
             model.run(args.steps)
         _bracket(comm)
         t1 = time.perf_counter()
-        return _max_over_ranks(comm, t1 - t0)
+        el = _max_over_ranks(comm, t1 - t0)
+        if args.dump_outputs:
+            # now, before any post-timing check advances or rewrites the fields
+            outs.clear()
+            outs.update(_take_outputs(model, nprocs))
+        return el
 
+    outs = {}  # --dump-outputs: what the last timed step of the (last) timed region left
     warm_load()
     elapsed = timed_region()
     H.check_transport()
     if hasattr(model, "check"):
         model.check()
-    # After the timed region: prove the steps that were timed computed the
+    # After the timed region (--full): prove the steps that were timed computed the
     # right field, and fail closed if not (a wrong field never yields a number).
     #  1. fused exchange: K fused vs K update_halo_ steps from the state the
     #     timed steps left, bitwise; on a mismatch the fused exchange is
@@ -1449,7 +1530,7 @@ def main():
     #     on a mismatch the run is re-timed on the next validated schedule, and
     #     fails (no JSON line) when none is left.
     fused_post = None
-    if getattr(model, "fused", False):
+    if args.full and getattr(model, "fused", False):
         PH.enter("post:fused", _path_key(model), deadline=600)
         n_post = max(args.steps, FUSED_KEEP_CHECK_STEPS)
         ok = _fused_check(model, comm, log, nchk=n_post, inject="fused_post")
@@ -1466,7 +1547,7 @@ def main():
             elapsed = timed_region()
             H.check_transport()
     post_valid = None
-    if nprocs > 1:
+    if args.full and nprocs > 1:
         PH.enter("post:transport", _path_key(model), deadline=300)
         post_valid = post_validate(field(), comm, log, on_gpu)
         tried = [(post_valid["transport"], post_valid["schedule"])]
@@ -1512,8 +1593,10 @@ def main():
     if getattr(model, "fused", False):
         model.sync_halo()
     finite = bool(torch.isfinite(field()).all().item())
+    if args.dump_outputs:
+        _write_outputs(args.dump_outputs, outs, me)
     phase_ms = None
-    if on_gpu and (not is2d and nprocs > 1 or args.loopback):
+    if args.full and on_gpu and (not is2d and nprocs > 1 or args.loopback):
         # stencil vs halo split of a few eager steps (events on the stream)
         from igg.utils.trace import PhaseTimer
 
@@ -1523,7 +1606,7 @@ def main():
         phase_ms = {k: v["mean_ms"] for k, v in model.timer.summary().items()}
         model.timer = None
     gather_ms = None
-    if gather_every > 0:
+    if args.full and gather_every > 0:
         # two blocking gathers, both reported: the first after the timed
         # region may still pay one-time costs (staging chunks of the blocking
         # form, peer mappings), the second is the steady-state cost
@@ -1554,6 +1637,9 @@ def main():
             "config": {
                 "model": cfg["model"],
                 "bench_config": args.config,
+                "full": bool(args.full),
+                "outputs_dumped": ({"dir": args.dump_outputs, "arrays": {k: list(v.shape) for k, v in outs.items()},
+                                    "warm_load_steps": warm["extra"]} if args.dump_outputs else None),
                 "global_batch": nprocs,
                 "seq_len": n,
                 "parallelism": f"spatial {dims[0]}x{dims[1]}x{dims[2]}",

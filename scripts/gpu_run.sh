@@ -7,7 +7,8 @@
 #   KIND  smoke                      __graft_entry__.smoke()
 #         pytest  [pytest args]      python -u -m pytest -x -q --timeout 120 (-m gpu unless -m given;
 #                                    --kor=a,b,c for -k "a or b or c")
-#         bench   [bench.py args]    python bench.py ... (prints the JSON summary line)
+#         bench   [bench.py args]    python bench.py ... (prints the JSON summary line; pass --full for
+#                                    the post-timing checks summarised after the step)
 #         py      script.py [args]   any python script of the repo
 #         prof    [bench.py args]    rocprofv3 --kernel-trace --stats around bench.py
 #         profpy  script.py [args]   the same around any python script of the repo

@@ -29,7 +29,7 @@ def _run(args, timeout=150, **env):
 def test_metric_label_says_what_value_is(n):
     """The metric label states the value's semantics (whole-job aggregate), and
     the value is n_gpus x the per-GPU T_eff (also at N=1)."""
-    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1"])
+    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert rec["metric"].startswith("effective GB/s per GPU + weak-scaling parallel efficiency")  # BASELINE.json
     assert "whole-job aggregate" in rec["metric"] and "sum of the per-GPU T_eff" in rec["metric"]
@@ -45,7 +45,7 @@ def test_post_validation_fails_closed():
     """A mismatch in the post-timing validation (injected on rank 0) leaves no
     schedule to fall back to in the CPU plumbing mode: the bench fails and
     prints no number."""
-    r, rec = _run(["--gpus", "2", "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1"],
+    r, rec = _run(["--gpus", "2", "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1", "--full"],
                   IGG_BENCH_INJECT="post_validation")
     assert r.returncode != 0
     assert rec is None
@@ -58,7 +58,7 @@ def test_stencil_post_check_fails_closed(n):
     starting state (on a GPU through a second compiled stencil variant) and
     compared bitwise: a mismatch (injected on rank 0) means no result line,
     at N = 1 too."""
-    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1"],
+    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1", "--full"],
                   IGG_BENCH_INJECT="stencil_post")
     assert r.returncode != 0
     assert rec is None
@@ -66,7 +66,7 @@ def test_stencil_post_check_fails_closed(n):
 
 
 def test_stencil_post_check_recorded_at_n1():
-    r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1"])
+    r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     sp = rec["config"]["stencil_post_check"]
     assert sp["result"] == "ok" and sp["steps"] == 3
@@ -146,7 +146,7 @@ def test_share_gpu_post_timing_checks(inject):
     injected fused mismatch fails closed (fused dropped, region re-timed on the
     update_halo_ path, the result still validated)."""
     r, rec = _run(["--gpus", "2", "--share-gpu", "--fused", "on", "--n", "96", "--steps", "20", "--warmup", "2",
-                   "--launch-timeout", "240"], timeout=280, IGG_BENCH_INJECT=inject,
+                   "--launch-timeout", "240", "--full"], timeout=280, IGG_BENCH_INJECT=inject,
                   IGG_FUSED_CANDIDATES="0/8/3,42/12/2", IGG_STENCIL_VARIANT="0")
     assert r.returncode == 0, r.stderr[-3000:]
     c = rec["config"]
@@ -166,7 +166,7 @@ def test_efficiency_measured_in_the_same_job(n):
     """config.efficiency: interleaved pairs of the 1-GPU run's local problem
     (plain stencil, no exchange) and the real step, on the same processes;
     value = median t_local / median t_step, with per-rank numbers."""
-    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1"])
+    r, rec = _run(["--gpus", str(n), "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     e = rec["config"]["efficiency"]
     assert e is not None and e["pairs"] >= 5 and e["steps"] % 2 == 0
@@ -188,7 +188,7 @@ def test_nothing_between_warm_load_and_bracket():
     load, and the timed region's bracket follows the warm load directly (round
     4 lost 2.9 % of the driver's 20-step number to a snapshot in between); the
     stencil post check replays the warm load + the timed steps."""
-    r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1"])
+    r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     order = rec["config"]["stage_order"]
     i = order.index("timed")
@@ -271,3 +271,67 @@ def test_efficiency_phase_leaves_a_consistent_state(model):
                 assert torch.equal(lo, T.select(d, T.shape[d] - 2)) and torch.equal(hi, T.select(d, 1))
     finally:
         igg.finalize_global_grid(finalize_MPI=False)
+
+
+def test_plain_run_does_only_the_headline():
+    """Without --full nothing beside the headline figure runs: no efficiency
+    phase, no snapshot, no post-timing check; the result line keeps its keys."""
+    r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    c = rec["config"]
+    assert c["full"] is False and c["stage_order"] == ["warm_load", "timed"]
+    assert c["efficiency"] is None and c["stencil_post_check"] is None and c["outputs_dumped"] is None
+    assert rec["steps"] == 4 and rec["ms_per_step"] == c["t_it_ms"] > 0
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert key in rec
+
+
+def test_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the field of the last timed step; two runs with the
+    same arguments write the same values, and they are those of W + K steps
+    from the model's initial condition."""
+    import numpy as np
+    import torch
+
+    import igg
+    from igg.models.diffusion3d import Diffusion3D
+
+    dumps = []
+    for d in ("a", "b"):
+        r, rec = _run(["--gpus", "1", "--device", "cpu", "--n", "20", "--steps", "4", "--warmup", "1",
+                       "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert rec["config"]["outputs_dumped"]["arrays"] == {"T": [20, 20, 20]}
+        assert os.listdir(tmp_path / d) == ["T.npy"]
+        dumps.append(np.load(tmp_path / d / "T.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (20, 20, 20)
+    assert np.array_equal(dumps[0], dumps[1])
+    igg.init_global_grid(20, 20, 20, quiet=True, init_MPI=False, device_type="none")
+    try:
+        m = Diffusion3D(dtype=torch.float64, device="cpu")
+        m.run(1 + 4)
+        assert np.array_equal(m.T.numpy(), dumps[0])
+    finally:
+        igg.finalize_global_grid(finalize_MPI=False)
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """A field above its share of DUMP_MAX_BYTES is dumped as the same sorted
+    sample of its flattened entries every time."""
+    import importlib.util as ilu
+
+    import torch
+
+    spec = ilu.spec_from_file_location("bench_mod", BENCH)
+    b = ilu.module_from_spec(spec)
+    spec.loader.exec_module(b)
+
+    class _M:
+        T = torch.arange(5 * 6 * 7, dtype=torch.float32).view(5, 6, 7)
+
+    whole = b._take_outputs(_M(), 1)
+    assert torch.equal(whole["T"], _M.T) and whole["T"].data_ptr() != _M.T.data_ptr()
+    b.DUMP_MAX_BYTES = 2 * 40 * 4  # two ranks' shares of 40 float32 each
+    s1, s2 = b._take_outputs(_M(), 2)["T"], b._take_outputs(_M(), 2)["T"]
+    assert s1.shape == (40,) and s1.dtype == torch.float32 and torch.equal(s1, s2)
+    assert bool((s1[1:] >= s1[:-1]).all()) and 0 <= s1.min() and s1.max() < 210  # entry values = flat indices

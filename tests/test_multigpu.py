@@ -196,7 +196,7 @@ def test_bench_self_launch_validates_every_transport(nprocs):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["IGG_BENCH_AB_BUDGET"] = "40"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nprocs), "--n", "128",
-                        "--steps", "20", "--warmup", "2", "--launch-timeout", str(max(20, int(t) - 20))],
+                        "--steps", "20", "--warmup", "2", "--full", "--launch-timeout", str(max(20, int(t) - 20))],
                        capture_output=True, text=True, timeout=t, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -87,7 +87,7 @@ def _json(stdout):
     return json.loads(lines[0]) if lines else None
 
 
-ARGS = ["--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1"]
+ARGS = ["--device", "cpu", "--n", "20", "--steps", "3", "--warmup", "1", "--full"]
 
 
 def test_self_launch_survives_an_injected_hang():
