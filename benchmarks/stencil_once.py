@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Run selected stencil variants a few times on n^3 (for rocprofv3 counters)."""
+"""Run selected stencil variants a few times on n^3 (for rocprofv3 counters);
+``--twostep FORMS`` launches the two-step pass (ms per PASS = two steps)."""
 import argparse
 import os
 import sys
@@ -16,6 +17,9 @@ ap.add_argument("--variants", default="0")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--dtype", default="float64")
 ap.add_argument("--rounds", default="0", help="grid residency rounds per launch (list; 0 = default)")
+ap.add_argument("--twostep", default="", help="two-step forms to launch (list, e.g. 0,1,2), after the variants")
+ap.add_argument("--no-variants", action="store_true", help="launch no single-step variant (profile the pass alone)")
+ap.add_argument("--halo-z", action="store_true", help="whole-line z-edge stores")
 ap.add_argument("--calib", action="store_true", help="also run T2.copy_(T) (known bytes) for counter calibration")
 ap.add_argument("--placement", action="store_true",
                 help="fields on the fastest of the placement probe's candidate carves (utils/placement.py)")
@@ -44,16 +48,27 @@ else:
     Cp = 1 + torch.rand((n, n, n), dtype=dt, device="cuda")
     T2 = T.clone()
 s = torch.cuda.current_stream().cuda_stream
-for v in [int(x) for x in a.variants.split(",")]:
+for v in ([] if a.no_variants else [int(x) for x in a.variants.split(",")]):
     for gr in [int(x) for x in a.rounds.split(",")]:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.reps):
             native.diffusion3d(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), [n, n, n], [1.0, 1.0, 1.0], 0.01,
-                               T.element_size(), [((1, 1, 1), (n - 1, n - 1, n - 1))], True, v, s, gr)
+                               T.element_size(), [((1, 1, 1), (n - 1, n - 1, n - 1))], True, v, s, gr, a.halo_z)
         e1.record()
         e1.synchronize()
         print(f"variant {v} rounds {gr}: {e0.elapsed_time(e1) / a.reps:.5f} ms per launch", flush=True)
+for f in [int(x) for x in a.twostep.split(",") if x]:
+    for gr in [int(x) for x in a.rounds.split(",")]:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            native.diffusion3d_twostep(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), [n, n, n], [1.0, 1.0, 1.0], 0.01,
+                                       T.element_size(), f, s, gr, a.halo_z)
+        e1.record()
+        e1.synchronize()
+        print(f"twostep form {f} rounds {gr}: {e0.elapsed_time(e1) / a.reps:.5f} ms per pass "
+              f"({e0.elapsed_time(e1) / a.reps / 2:.5f} per step)", flush=True)
 if a.calib:
     for _ in range(a.reps):
         T2.copy_(T)  # reads n^3 and writes n^3 elements

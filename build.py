@@ -8,7 +8,12 @@ snapshot to the GPU box. Incremental: objects are rebuilt only when a source or
 any header is newer. No torch headers are used (the runtime takes raw
 pointers), so a full build takes seconds.
 
-Usage: ``python build.py [--clean] [-j N] [--debug] [--asan] [--probes]``
+Usage: ``python build.py [--clean] [-j N] [--debug] [--asan] [--probes] [--smoke-unit NAME]``
+
+``--smoke-unit NAME`` (e.g. ``stencil2_kernels``) only compiles
+``csrc/kernels/NAME.hip`` for gfx950 with the build's flags - no GPU needed -
+prints each kernel's registers, LDS and scratch as the compiler reports them,
+and fails if any kernel of the unit uses scratch.
 
 ``--probes`` also compiles the measurement-only kernel forms of rounds 1-2
 (stencil tilings and fused variants that lost their A/B, timing probes whose
@@ -130,6 +135,29 @@ def build(jobs: int | None = None, debug: bool = False, asan: bool = False, verb
     return out
 
 
+def smoke_unit(name: str) -> None:
+    """Compile-only check of one kernel unit (see the module docstring)."""
+    import re
+    import tempfile
+
+    src = CSRC / "kernels" / f"{name}.hip"
+    if not src.exists():
+        raise SystemExit(f"no such unit: {src.relative_to(ROOT)}")
+    flags = ["-std=c++17", "-fPIC", "-O3", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]
+    with tempfile.TemporaryDirectory() as tmp:
+        _, err = _compile(src, Path(tmp) / f"{name}.o", flags)
+    kernels = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+                         r"LDS Size \[bytes/block\]: (\d+)", err, re.S)
+    if not kernels:
+        raise SystemExit(f"{name}: the compiler reported no kernel")
+    for fn, vgpr, scratch, lds in kernels:
+        print(f"{name}: {fn}: {vgpr} VGPRs, {lds} B LDS, {scratch} B scratch")
+    bad = [fn for fn, _v, scratch, _l in kernels if int(scratch)]
+    if bad:
+        raise SystemExit(f"{name}: scratch in {', '.join(bad)}")
+    print(f"{name}: {len(kernels)} kernels compiled for {ARCH}, none with scratch")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--clean", action="store_true")
@@ -138,7 +166,12 @@ def main() -> None:
     ap.add_argument("--asan", action="store_true")
     ap.add_argument("--probes", action="store_true", help="also compile the measurement-only kernel forms")
     ap.add_argument("-v", "--verbose", action="store_true")
+    ap.add_argument("--smoke-unit", metavar="NAME", default=None,
+                    help="compile-only check of csrc/kernels/NAME.hip (e.g. stencil2_kernels); builds nothing else")
     a = ap.parse_args()
+    if a.smoke_unit:
+        smoke_unit(a.smoke_unit)
+        return
     if a.clean:
         shutil.rmtree(BUILD, ignore_errors=True)
         ext_path().unlink(missing_ok=True)

@@ -753,6 +753,29 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("t2"), py::arg("t"), py::arg("cp"), py::arg("n"), py::arg("rd2"), py::arg("dtlam"),
         py::arg("elem_bytes"), py::arg("tiling"), py::arg("stream") = 0, py::arg("rounds") = 0,
         py::arg("halo_z") = false);
+  // Two time steps in one pass (stencil2_kernels.hip): whole inner box, GPU only.
+  m.def("diffusion3d_twostep",
+        [](uintptr_t t2, uintptr_t t, uintptr_t cp, const Int3& n, const std::array<double, 3>& rd2,
+           double dtlam, int elem_bytes, int form, uintptr_t stream, int rounds, bool halo_z) {
+          TraceRange tr("igg.diffusion3d_twostep");
+          DiffusionArgs a{t2, t, cp, {n[0], n[1], n[2]}, {rd2[0], rd2[1], rd2[2]}, dtlam, elem_bytes, rounds, halo_z,
+                          form};
+          launch_diffusion3d_twostep(a, as_stream(stream));
+        },
+        py::arg("t2"), py::arg("t"), py::arg("cp"), py::arg("n"), py::arg("rd2"), py::arg("dtlam"),
+        py::arg("elem_bytes"), py::arg("form") = 0, py::arg("stream") = 0, py::arg("rounds") = 0,
+        py::arg("halo_z") = false);
+  m.def("diffusion3d_twostep_ok",
+        [](const Int3& n, int elem_bytes, int form) {
+          DiffusionArgs a{0, 0, 0, {n[0], n[1], n[2]}, {1.0, 1.0, 1.0}, 0.0, elem_bytes, 0, false, form};
+          return diffusion3d_twostep_ok(a);
+        },
+        py::arg("n"), py::arg("elem_bytes"), py::arg("form") = 0);
+  m.def("diffusion3d_twostep_forms", []() {
+    std::vector<std::string> v;
+    for (int i = 0; i < diffusion3d_twostep_num_forms(); ++i) v.push_back(diffusion3d_twostep_form_name(i));
+    return v;
+  });
   m.def("diffusion3d_fused_variant_ok", &diffusion3d_fused_variant_ok);
   m.def("diffusion3d_variant_compiled", &stencil_variant_compiled,
         "Whether stencil variant v is compiled in this build (measurement-only ones: build.py --probes).");

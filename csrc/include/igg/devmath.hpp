@@ -31,4 +31,18 @@ __device__ __forceinline__ T diffusion_point(T c, T xm, T xp, T ym, T yp, T zm, 
   return fmad(dtlam / cp, lap, c);
 }
 
+// The same operations with the quotient q = dtlam/cp given: a kernel that
+// updates one point twice (the two-step pass, stencil2_kernels.hip) divides
+// once. Keep the two bodies identical.
+template <typename T>
+__device__ __forceinline__ T diffusion_point_q(T c, T xm, T xp, T ym, T yp, T zm, T zp, T q, T rdx2, T rdy2,
+                                               T rdz2) {
+  const T m2 = T(-2);
+  const T dx = fmad(m2, c, xp) + xm;
+  const T dy = fmad(m2, c, yp) + ym;
+  const T dz = fmad(m2, c, zp) + zm;
+  const T lap = fmad(dz, rdz2, fmad(dy, rdy2, dx * rdx2));
+  return fmad(q, lap, c);
+}
+
 }  // namespace igg

@@ -42,6 +42,7 @@ struct DiffusionArgs {
   // t2's z halo concurrently. 1024^3 f32: -5.5..-6.8 % per step, 512^3 f64:
   // up to -2.9 % (profiles/r4_halo_z/).
   bool halo_z = false;
+  int form = 0;             // two-step pass only: tiling (diffusion3d_twostep_num_forms)
 };
 
 // Number of tuned kernel variants (see stencil_kernels.hip); variant 0 = default.
@@ -57,6 +58,23 @@ int diffusion3d_get_rounds();
 
 void launch_diffusion3d(const DiffusionArgs& a, const std::vector<Box>& boxes, int variant,
                         hipStream_t stream);
+
+// Blocks a launch of `kernel` (`block` threads) aims at: `rounds` as in
+// DiffusionArgs::rounds (0 = the global default of diffusion3d_set_rounds).
+int64_t diffusion3d_target_blocks(const void* kernel, int block, int rounds);
+
+// Two time steps in one pass over memory (stencil2_kernels.hip): after the
+// launch t2 holds, bitwise, what launch_diffusion3d t -> tmp -> t2 on the whole
+// inner box leaves, tmp's boundary planes being t's (fixed boundary values, no
+// halo exchange between the two steps: a rank without neighbours). t and cp are
+// read only; t2's boundary planes are not written, except its z halo elements
+// with halo_z (t's values, as in the single-step kernel). a.form selects the
+// tiling. _ok: the pass has a form for this shape and element size; the launch
+// fails where it is false (callers run two single steps instead).
+int diffusion3d_twostep_num_forms();
+const char* diffusion3d_twostep_form_name(int form);
+bool diffusion3d_twostep_ok(const DiffusionArgs& a);
+void launch_diffusion3d_twostep(const DiffusionArgs& a, hipStream_t stream);
 
 // Fused halo exchange (see fused.hpp): the inner-box update additionally
 // stores its send planes into the receivers' arena regions (`out`, 0 = no

@@ -21,6 +21,7 @@
 
 #include "igg/devmath.hpp"
 #include "igg/stencil.hpp"
+#include "igg/xcd.hpp"
 
 namespace igg {
 namespace {
@@ -45,13 +46,6 @@ struct KArgs {
   T rdx2, rdy2, rdz2, dtlam;
   int halo_z;  // DiffusionArgs::halo_z: z-edge lanes store whole vectors (halo elements copied from t)
 };
-
-__device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nb) {
-  // Bijective round-robin inversion (cdna_hip_programming.md §5 'XCD swizzle
-  // must be bijective'): blocks dealt to XCD k get the contiguous id range k*q..
-  const int64_t q = nb / 8, r = nb % 8, xcd = b % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-}
 
 template <typename T, int BY, int RY, bool XCD>
 __global__ void __launch_bounds__(64 * BY)
@@ -532,6 +526,14 @@ bool stencil_variant_compiled(int v) {
       return false;
   }
 #endif
+}
+
+int64_t diffusion3d_target_blocks(const void* kernel, int block, int rounds) {
+  const int saved = g_call_rounds;
+  g_call_rounds = rounds;
+  const int64_t t = target_for(kernel, block);
+  g_call_rounds = saved;
+  return t;
 }
 
 int diffusion3d_num_variants() { return NVARIANTS; }

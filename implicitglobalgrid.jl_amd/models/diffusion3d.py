@@ -46,6 +46,9 @@ from ..utils.tools import coords_g, nx_g, ny_g, nz_g
 # Time steps per captured hipGraph (even): one replay launch (~9 us) per
 # GRAPH_STEPS steps instead of per 2 (profiles/r1_fused/graph_gaps.txt).
 GRAPH_STEPS = 10
+# While the two-step pass is on a graph holds passes, and an even number of
+# them hands the ping-pong buffers back in their roles: 20 steps = 10 passes.
+TWOSTEP_GRAPH_STEPS = 20
 # Candidates re-timed by the autotune's ping-pong stage (_choose_variant).
 PINGPONG_FRONT = 4
 # Whole-line z-edge stores of the full-box steps (ops.stencil.diffusion3d_
@@ -69,7 +72,22 @@ class Diffusion3D:
     ``T2 = T + dt*lam/Cp * laplace(T)`` by one fused HIP kernel, then
     ``update_halo_(T2)`` (or the fused exchange, ``set_fused``), ping-pong T/T2.
     ``step``/``run`` advance, ``capture`` records hipGraphs, ``save``/``restore``
-    checkpoint."""
+    checkpoint.
+
+    Two-step pass (``two_step``; IGG_STENCIL_TWOSTEP=auto|0|1): where nothing
+    looks at the field between steps and ``update_halo_`` has nothing to do -
+    ``run``/``capture`` on a GPU model without neighbours, periodic
+    self-exchange or loopback, not fused, not overlapped, no timer - pairs of
+    steps run as one kernel pass that reads T and Cp once and writes the field
+    two steps later (ops.stencil.diffusion3d_twostep_; bitwise the values of
+    two single steps). ``step``/``local_step`` stay single steps. ``variant``
+    names the single-step kernel: assigning another one than the selection ran
+    with switches the pass off until the original is assigned back.
+
+    ``T2`` is the other ping-pong buffer: its boundary planes always equal
+    ``T``'s fixed boundary values; its interior is the field of one step ago
+    after a single step and of TWO steps ago after a two-step pass (it is
+    rewritten by whatever runs next either way)."""
 
     def __init__(self, *, dtype=torch.float64, device=None, lam: float = 1.0, cp_min: float = 1.0,
                  lx: float = 10.0, ly: float = 10.0, lz: float = 10.0, overlap: bool = False,
@@ -86,7 +104,15 @@ class Diffusion3D:
         self.dy = ly / (ny_g() - 1)
         self.dz = lz / (nz_g() - 1)
         self.dt = min(self.dx ** 2, self.dy ** 2, self.dz ** 2) * cp_min / lam / 8.1
-        self.variant = variant
+        self._variant = variant
+        # Two-step pass: whether the selection kept it, its tiling (ops.stencil
+        # TWOSTEP_FORMS) and grid rounds, the A/B's ms per step ("single" and
+        # "t<form>@r<rounds>"), and the variant the selection ran with.
+        self._two_step = False
+        self._two_step_variant = None
+        self.two_step_form = 0
+        self.two_step_rounds = 0
+        self.two_step_times = {}
         self.rounds = 0  # grid residency rounds of the full-interior launch (0: library default)
         self.halo_z = HALO_Z  # whole-line z-edge stores of the full-interior launch (autotuned per variant)
         self.variant_times = None  # per-variant ms when autotuned (see _choose_variant)
@@ -215,6 +241,51 @@ class Diffusion3D:
         self._graph_parity = 0
         self._graph_cfg = None  # fused (variant, mode, rounds) of the capture
         self._graph_T = 0  # T's buffer when the graph was captured
+        self._graph_two = None  # two-step (form, rounds) of the capture, None: single steps
+        _select_two_step(self)
+
+    @property
+    def variant(self):
+        """The single-step kernel variant (ops.stencil)."""
+        return self._variant
+
+    @variant.setter
+    def variant(self, v) -> None:
+        self._variant = v
+
+    @property
+    def two_step(self) -> bool:
+        """The two-step pass is selected and ``variant`` is still the one it
+        was selected against (whether a given ``run`` uses it: ``_two_step_now``)."""
+        return self._two_step and self._variant == self._two_step_variant
+
+    @two_step.setter
+    def two_step(self, flag: bool) -> None:
+        self._two_step = bool(flag)
+        self._two_step_variant = self._variant
+
+    def _two_step_now(self) -> bool:
+        """Eligibility of the two-step pass right now: selected, GPU, the
+        plain step (not fused, not overlapped, no phase timer), update_halo_
+        would do nothing (no neighbour, periodic self-exchange or loopback on
+        any side of the grid as it is now), and the kernel has a form for the
+        shape."""
+        if not self.two_step or self.device.type != "cuda":
+            return False
+        if self.fused or self.overlap or self.timer is not None:
+            return False
+        return _no_exchange() and stencil.twostep_ok(self.T, self.two_step_form)
+
+    def _two_step_key(self):
+        return (self.two_step_form, self.two_step_rounds) if self._two_step_now() else None
+
+    def _pass(self) -> None:
+        """Two time steps in one pass (callers checked ``_two_step_now``)."""
+        T, T2 = self.T, self.T2
+        stencil.diffusion3d_twostep_(T2, T, self.Cp, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy, dz=self.dz,
+                                     form=self.two_step_form, rounds=self.two_step_rounds, halo_z=HALO_Z)
+        self.T, self.T2 = T2, T
+        self._warm = True
 
     @property
     def can_fuse(self) -> bool:
@@ -486,19 +557,24 @@ class Diffusion3D:
         self.T, self.T2 = T2, T
 
     def capture(self, steps: int = None) -> None:
-        """Record ``steps`` (even, default GRAPH_STEPS) time steps in a hipGraph for ``run``.
+        """Record ``steps`` (even, default GRAPH_STEPS; TWOSTEP_GRAPH_STEPS
+        while the two-step pass is on) time steps in a hipGraph for ``run``.
 
         A step is a chain of launches (stencil, pack, RCCL group, unpack per
         dimension; or fused stencil + sync) whose gaps are host launch latency;
         replaying a graph removes that latency, and a graph replay costs ~9 us
         to launch on MI355X (profiles/r1_fused/), so several steps are captured
         per graph. An even count puts the ping-pong buffers back in their roles
-        after every replay. Needs one eager step first (halo buffers, plan
+        after every replay; with the two-step pass an even number of PASSES is
+        recorded, closed by two single steps when steps % 4 == 2. Needs one eager step first (halo buffers, plan
         cache and kernel variant are set up outside the capture); ``capture``
         performs that step itself if none ran yet (and one fused step if the
         fused arena does not hold T's halos).
         """
-        steps = GRAPH_STEPS if steps is None else int(steps)
+        two = self._two_step_key()
+        if steps is None:
+            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
+        steps = int(steps)
         if steps < 2 or steps % 2:
             raise ValueError("Diffusion3D.capture: steps must be even and >= 2")
         if self.device.type != "cuda":
@@ -510,7 +586,12 @@ class Diffusion3D:
         if self.fused and not self._fprimed:
             self.step()  # captured fused steps read the arena: it must hold T's halos
         def record():
-            for _ in range(steps):
+            singles = steps
+            if two is not None:
+                singles = steps % 4
+                for _ in range(steps // 4 * 2):
+                    self._pass()
+            for _ in range(singles):
                 self._step()  # no exit barrier inside the graph: run() drains once
 
         self.graph = None
@@ -522,12 +603,15 @@ class Diffusion3D:
         self._graph_cfg = self._fused_cfg()
         self._graph_parity = self._fstep % 2
         self._graph_T = self.T.data_ptr()
+        self._graph_two = two
 
     def run(self, nt: int) -> None:
         """Advance ``nt`` steps (by graph replays of ``graph_steps`` steps if
         captured); in fused mode one exit barrier at the end (``_drain``)."""
         ran = nt > 0
-        if self.graph is not None and self._graph_fused == self.fused and self._graph_cfg == self._fused_cfg():
+        two = self._two_step_key()
+        if self.graph is not None and self._graph_fused == self.fused and self._graph_cfg == self._fused_cfg() \
+                and self._graph_two == two:
             # The captured steps have their buffer roles baked in (T of the
             # capture is read first) and, fused, their arena halves too: they
             # assume a primed arena, no pending entry barrier and the
@@ -546,6 +630,10 @@ class Diffusion3D:
                 if self.fused:
                     self._fstep += k * (nt // k)
                 nt %= k
+        if two is not None:
+            for _ in range(nt // 2):
+                self._pass()
+            nt %= 2
         for _ in range(nt):
             self._step()
         if ran:
@@ -567,6 +655,48 @@ class Diffusion3D:
     def a_eff_bytes(self) -> int:
         """A_eff = (2*D_u + D_k) * n_local * sizeof(T) with D_u = D_k = 1."""
         return 3 * self.T.numel() * self.T.element_size()
+
+
+def _no_exchange() -> bool:
+    """update_halo_ would do nothing: the grid has no neighbour on any side
+    (a periodic single process and the loopback emulation are their own
+    neighbours and do exchange)."""
+    from ..parallel import halo as H
+
+    gg = _grid.global_grid()
+    return not H.loopback_active() and all(int(gg.neighbors[s, d]) == -1 for s in range(2) for d in range(3))
+
+
+def _select_two_step(m: "Diffusion3D") -> None:
+    """Decide the two-step pass for this model (IGG_STENCIL_TWOSTEP): 0 off,
+    1 on where eligible (form 0, library grid), auto (default): the chosen
+    single-step kernel against every two-step form x GRID_ROUNDS in the time
+    loop's ping-pong shape; the pass is kept only if its time PER STEP is
+    below the single-step kernel's."""
+    env = os.environ.get("IGG_STENCIL_TWOSTEP", "auto").strip().lower()
+    if env not in ("auto", "0", "1"):
+        raise ValueError(f"IGG_STENCIL_TWOSTEP must be auto, 0 or 1, got {env!r}")
+    m.two_step = False
+    if env == "0" or m.device.type != "cuda" or m.variant is None or not _no_exchange():
+        return
+    forms = [f for f in stencil.TWOSTEP_FORMS if stencil.twostep_ok(m.T, f)]
+    if not forms:
+        return
+    if env == "1":
+        m.two_step_form, m.two_step_rounds = forms[0], 0
+        m.two_step = True
+        return
+    rd2 = [1.0 / m.dx ** 2, 1.0 / m.dy ** 2, 1.0 / m.dz ** 2]
+    boxes = [(list(b[0]), list(b[1])) for b in m.inner]
+    cands = [(f, r, HALO_Z) for f in forms for r in stencil.GRID_ROUNDS]
+    single, t = stencil.time_twostep_pingpong(m.T2, m.T, m.Cp, rd2, m.dt * m.lam, boxes,
+                                              (int(m.variant), int(m.rounds), bool(m.halo_z)), cands)
+    m.two_step_times = {"single": round(single, 5)}
+    m.two_step_times.update({f"t{f}@r{r}": round(x, 5) for (f, r, _hz), x in t.items()})
+    best = min(t, key=t.get)
+    if t[best] < single:
+        m.two_step_form, m.two_step_rounds = int(best[0]), int(best[1])
+        m.two_step = True
 
 
 def _hw_queues() -> int | None:

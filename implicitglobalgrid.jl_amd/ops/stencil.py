@@ -199,6 +199,86 @@ def diffusion3d_(T2, T, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: 
                        T.element_size(), boxes, dev, v, s, rounds, bool(halo_z) and dev)
 
 
+# Tilings of the two-step pass (csrc/kernels/stencil2_kernels.hip). They are
+# not part of the variant index space: a variant names a single-step kernel.
+TWOSTEP_FORMS = tuple(range(len(native.diffusion3d_twostep_forms())))
+
+
+def twostep_ok(T, form: int = 0) -> bool:
+    """Whether two-step form ``form`` can run on ``T`` (GPU, float32/float64,
+    3-D contiguous, rows a multiple of the 16-byte vector)."""
+    if not (T.is_cuda and T.dim() == 3 and T.is_contiguous() and T.dtype in (torch.float32, torch.float64)):
+        return False
+    return bool(native.diffusion3d_twostep_ok(list(T.shape), T.element_size(), int(form)))
+
+
+def diffusion3d_twostep_(T2, T, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: float,
+                         form: int = 0, rounds: int = 0, halo_z: bool = False, stream: int | None = None) -> None:
+    """Two diffusion updates in one pass over memory: afterwards ``T2`` holds,
+    bitwise, what ``diffusion3d_(tmp, T, Cp)`` then ``diffusion3d_(T2, tmp, Cp)``
+    on the whole interior leave, where ``tmp``'s boundary planes equal ``T``'s
+    (fixed boundary values, no halo exchange between the two steps). ``T`` and
+    ``Cp`` are only read; ``T2``'s boundary planes are not written (``halo_z``
+    as in ``diffusion3d_``). GPU only; raises ``IGGError`` where ``twostep_ok``
+    is false (callers then run two single steps)."""
+    _check(T2, T, Cp)
+    if not T.is_cuda:
+        raise IGGError("diffusion3d_twostep: GPU tensors only (there is no host two-step kernel)")
+    if not twostep_ok(T, form):
+        raise IGGError(f"diffusion3d_twostep: form {form} cannot run shape {tuple(T.shape)} {T.dtype}")
+    rd2 = [1.0 / (dx * dx), 1.0 / (dy * dy), 1.0 / (dz * dz)]
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    native.diffusion3d_twostep(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), list(T.shape), rd2, dt * lam,
+                               T.element_size(), int(form), s, int(rounds), bool(halo_z))
+
+
+def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, steps: int = 20, rounds: int = 5) -> tuple:
+    """Median ms PER STEP of the single-step candidate ``single`` (a
+    (variant, rounds, halo_z) triple) and of each two-step candidate (form,
+    rounds, halo_z), interleaved, in the time loop's ping-pong shape on the
+    model's own two buffers (``steps`` a multiple of 4: an even number of
+    passes). T is saved and restored; T2's interior is scribbled. Returns
+    (single ms, {candidate: ms})."""
+    n = list(T.shape)
+    s = torch.cuda.current_stream()
+    es = T.element_size()
+    backup = T.clone()
+
+    def run(c, k):
+        if c is None:
+            v, gr, hz = single
+            for j in range(k):
+                dst, src = (T2, T) if j % 2 == 0 else (T, T2)
+                native.diffusion3d(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, boxes, True,
+                                   v, s.cuda_stream, gr, hz)
+        else:
+            f, gr, hz = c
+            for j in range(k // 2):
+                dst, src = (T2, T) if j % 2 == 0 else (T, T2)
+                native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f,
+                                           s.cuda_stream, gr, hz)
+
+    order = [None] + list(candidates)
+    times = {c: [] for c in order}
+    try:
+        for c in order:
+            run(c, 4)
+        for _ in range(rounds):
+            for c in order:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                run(c, steps)
+                e1.record(s)
+                e1.synchronize()
+                times[c].append(e0.elapsed_time(e1) / steps)
+    finally:
+        T.copy_(backup)
+        torch.cuda.synchronize()
+        del backup
+    med = {c: sorted(t)[len(t) // 2] for c, t in times.items()}
+    return med.pop(None), med
+
+
 def diffusion3d_reference(T, Cp, *, lam, dt, dx, dy, dz) -> torch.Tensor:
     """Plain-PyTorch (fp64) reference of the reference example's 5 broadcasts."""
     T = T.double()
