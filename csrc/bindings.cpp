@@ -157,8 +157,10 @@ std::vector<Field> to_fields(const std::vector<FieldTuple>& ts) {
 }
 
 GridInfo make_grid(int64_t me, int64_t nprocs, const Int3& nxyz, const Int3& overlaps,
-                   const std::array<Int3, 2>& neighbors, const std::vector<int64_t>& peers) {
+                   const std::array<Int3, 2>& neighbors, const std::vector<int64_t>& peers,
+                   const Int3& halowidths) {
   GridInfo g;
+  g.halowidths = halowidths;
   g.me = me;
   g.nprocs = nprocs;
   g.nxyz = nxyz;
@@ -390,15 +392,25 @@ PYBIND11_MODULE(_igg_native, m) {
                           fc.s_inner, fc.contiguous, fc.bytes);
   });
 
+  m.def("slab_info", [](const FieldTuple& f, int dim, int64_t lo, int64_t w) {
+    const Field fd = to_field(f);
+    if (dim < 0 || dim >= NDIMS || w < 1 || lo < 0 || lo + w > fd.size[dim]) fail("slab_info: planes out of range");
+    const Face fc = slab(fd, dim, lo, w);
+    return py::make_tuple(reinterpret_cast<uintptr_t>(fc.base), fc.n_outer, fc.n_mid, fc.n_inner, fc.s_outer,
+                          fc.s_mid, fc.s_inner, fc.contiguous, fc.bytes);
+  });
+
   py::class_<GridInfo>(m, "GridInfo")
       .def(py::init(&make_grid), py::arg("me"), py::arg("nprocs"), py::arg("nxyz"),
-           py::arg("overlaps"), py::arg("neighbors"), py::arg("peers") = std::vector<int64_t>{})
+           py::arg("overlaps"), py::arg("neighbors"), py::arg("peers") = std::vector<int64_t>{},
+           py::arg("halowidths") = Int3{1, 1, 1})
       .def_readonly("peers", &GridInfo::peers)
       .def_readonly("has_peers", &GridInfo::has_peers)
       .def_readwrite("me", &GridInfo::me)
       .def_readwrite("nprocs", &GridInfo::nprocs)
       .def_readwrite("nxyz", &GridInfo::nxyz)
       .def_readwrite("overlaps", &GridInfo::overlaps)
+      .def_readwrite("halowidths", &GridInfo::halowidths)
       .def_readwrite("neighbors", &GridInfo::neighbors);
 
   // --- copies
@@ -417,6 +429,24 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("copies"), py::arg("elem_bytes"), py::arg("device"), py::arg("stream") = 0,
         py::arg("system") = false,
         "Batched strided 2-D copies; system: the put transport's system-scope (sc0 sc1) stores.");
+
+  m.def("copy3d",
+        [](const std::vector<std::array<int64_t, 9>>& boxes, const std::vector<std::pair<uintptr_t, uintptr_t>>& ptrs,
+           int elem_bytes, bool device, uintptr_t stream, bool system) {
+          if (boxes.size() != ptrs.size()) fail("copy3d: one (src, dst) pair per box");
+          std::vector<Copy3D> v;
+          for (size_t k = 0; k < boxes.size(); ++k) {
+            const auto& b = boxes[k];
+            v.push_back({reinterpret_cast<const char*>(ptrs[k].first), reinterpret_cast<char*>(ptrs[k].second),
+                         b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8]});
+          }
+          if (device) launch_copy3d(v, elem_bytes, as_stream(stream), system);
+          else host_copy3d(v, elem_bytes);
+        },
+        py::arg("boxes"), py::arg("ptrs"), py::arg("elem_bytes"), py::arg("device"), py::arg("stream") = 0,
+        py::arg("system") = false,
+        "Batched strided 3-extent copies (slab kernel): boxes are (n_outer, n_mid, n_inner, src strides, dst "
+        "strides), strides in elements.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")
@@ -568,7 +598,7 @@ PYBIND11_MODULE(_igg_native, m) {
   py::class_<HaloEngine>(m, "HaloEngine")
       .def(py::init<const GridInfo&>())
       .def_property_readonly("grid", [](HaloEngine& e) { return e.grid(); })
-      .def("set_grid", [](HaloEngine& e, const GridInfo& g) { e.grid() = g; })
+      .def("set_grid", &HaloEngine::set_grid)
       .def("set_transport", &HaloEngine::set_transport, py::arg("transport"), py::arg("device"))
       .def("clear_transport", [](HaloEngine& e, bool device) { e.set_transport(nullptr, device); })
       .def("transport_name", [](HaloEngine& e, bool device) {

@@ -29,17 +29,19 @@ int64_t max_halo_elems(const Field& f) {
 
 static void require_halo(const GridInfo& g, int dim, const Field& f) {
   if (ol(g, dim, f) < 2) fail("Incoherent arguments: ol(A,dim)<2.");
+  if (g.halowidths[dim] > 1 && ol(g, dim, f) < 2 * g.halowidths[dim])
+    fail("Incoherent arguments: ol(A,dim)<2*halowidths[dim].");
 }
 
 int64_t send_index(const GridInfo& g, int side, int dim, const Field& f) {
   require_halo(g, dim, f);
   const int64_t o = ol(g, dim, f);
-  return side == 0 ? o - 1 : f.size[dim] - o;
+  return side == 0 ? o - g.halowidths[dim] : f.size[dim] - o;
 }
 
 int64_t recv_index(const GridInfo& g, int side, int dim, const Field& f) {
   require_halo(g, dim, f);
-  return side == 0 ? 0 : f.size[dim] - 1;
+  return side == 0 ? 0 : f.size[dim] - g.halowidths[dim];
 }
 
 Face face(const Field& f, int dim, int64_t index) {
@@ -64,17 +66,40 @@ Face face(const Field& f, int dim, int64_t index) {
   return fc;
 }
 
+Face slab(const Field& f, int dim, int64_t lo, int64_t w) {
+  if (w == 1) return face(f, dim, lo);
+  Region r{};
+  for (int d = 0; d < NDIMS; ++d) {
+    r.lo[d] = d == dim ? lo : 0;
+    r.hi[d] = d == dim ? lo + w : f.size[d];
+  }
+  return region_face(f, r);
+}
+
 Face region_face(const Field& f, const Region& r) {
-  int ext[2] = {-1, -1}, k = 0;
+  int ext[3] = {-1, -1, -1}, k = 0;
   for (int d = 0; d < NDIMS; ++d)
-    if (r.hi[d] - r.lo[d] > 1) {
-      if (k == 2) fail("region_face: region has three non-singleton extents");
-      ext[k++] = d;
-    }
+    if (r.hi[d] - r.lo[d] > 1) ext[k++] = d;
   Face fc{};
   int64_t off = 0;
   for (int d = 0; d < NDIMS; ++d) off += r.lo[d] * f.stride[d];
   fc.base = reinterpret_cast<char*>(f.ptr) + off * f.elem_bytes;
+  if (k == 3) {
+    // Three extents (a slab of a wide halo, an edge or a corner of one):
+    // outer, mid, inner by decreasing stride (ties -> higher index inner).
+    std::sort(ext, ext + 3, [&](int a, int b) {
+      return f.stride[a] != f.stride[b] ? f.stride[a] > f.stride[b] : a < b;
+    });
+    fc.n_outer = r.hi[ext[0]] - r.lo[ext[0]];
+    fc.n_mid = r.hi[ext[1]] - r.lo[ext[1]];
+    fc.n_inner = r.hi[ext[2]] - r.lo[ext[2]];
+    fc.s_outer = f.stride[ext[0]];
+    fc.s_mid = f.stride[ext[1]];
+    fc.s_inner = f.stride[ext[2]];
+    fc.contiguous = fc.s_inner == 1 && fc.s_mid == fc.n_inner && fc.s_outer == fc.n_mid * fc.n_inner;
+    fc.bytes = static_cast<size_t>(fc.n_outer * fc.n_mid * fc.n_inner * f.elem_bytes);
+    return fc;
+  }
   int inner = -1, outer = -1;
   if (k == 2) {
     inner = f.stride[ext[0]] < f.stride[ext[1]] ? ext[0] : ext[1];
@@ -91,6 +116,45 @@ Face region_face(const Field& f, const Region& r) {
   fc.contiguous = fc.s_inner == 1 && fc.s_outer == fc.n_inner;
   fc.bytes = static_cast<size_t>(fc.n_outer * fc.n_inner * f.elem_bytes);
   return fc;
+}
+
+// Copies between a region and its packed image (memory order of the region).
+static Copy3D pack_copy(const Face& f, char* buf) {
+  return {f.base, buf, f.n_outer, f.n_mid, f.n_inner, f.s_outer, f.s_mid, f.s_inner,
+          f.n_mid * f.n_inner, f.n_inner, 1};
+}
+static Copy3D unpack_copy(const char* buf, const Face& f) {
+  return {buf, f.base, f.n_outer, f.n_mid, f.n_inner, f.n_mid * f.n_inner, f.n_inner, 1,
+          f.s_outer, f.s_mid, f.s_inner};
+}
+static Copy3D move_copy(const Face& s, const Face& d) {
+  return {s.base, d.base, s.n_outer, s.n_mid, s.n_inner, s.s_outer, s.s_mid, s.s_inner,
+          d.s_outer, d.s_mid, d.s_inner};
+}
+
+// Planes (every copy with n_mid == 1: all of a width-1 exchange) as 2-D copies.
+static bool as_planes(const std::vector<Copy3D>& cps, std::vector<Copy2D>& out) {
+  for (const Copy3D& c : cps)
+    if (c.n_mid != 1) return false;
+  out.reserve(cps.size());
+  for (const Copy3D& c : cps)
+    out.push_back({c.src, c.dst, c.n_outer, c.n_inner, c.src_so, c.src_si, c.dst_so, c.dst_si});
+  return true;
+}
+
+// One launch (device) or pass (host) over `cps`: the 2-D kernel when every
+// region is a plane, the slab kernel otherwise.
+static void run_copies(const std::vector<Copy3D>& cps, int eb, bool device, hipStream_t stream,
+                       bool system_fence = false, const ParityShift& parity = ParityShift{}) {
+  if (cps.empty()) return;
+  std::vector<Copy2D> planes;
+  if (as_planes(cps, planes)) {
+    if (device) launch_copy2d(planes, eb, stream, system_fence, parity);
+    else host_copy2d(planes, eb);
+  } else {
+    if (device) launch_copy3d(cps, eb, stream, system_fence, parity);
+    else host_copy3d(cps, eb);
+  }
 }
 
 // ---------------------------------------------------------------- BufferPool
@@ -144,7 +208,7 @@ void BufferPool::ensure(const std::vector<Field>& fields, bool device) {
   if (slots.size() < fields.size()) slots.resize(fields.size());
   for (size_t i = 0; i < fields.size(); ++i) {
     const Field& f = fields[i];
-    const size_t need = static_cast<size_t>(round_up(max_halo_elems(f), ALLOC_GRANULARITY) *
+    const size_t need = static_cast<size_t>(round_up(max_halo_elems(f) * width_, ALLOC_GRANULARITY) *
                                             f.elem_bytes);
     for (int n = 0; n < NNEIGHBORS; ++n) {
       grow(slots[i].send[n], need, device);
@@ -177,9 +241,17 @@ void BufferPool::free_all() {
 
 // ---------------------------------------------------------------- HaloEngine
 
-HaloEngine::HaloEngine(const GridInfo& g) : grid_(g) {
+HaloEngine::HaloEngine(const GridInfo& g) {
+  set_grid(g);
   const char* e = std::getenv("IGG_DEBUG_SYNC");
   debug_sync_ = e && *e && *e != '0';
+}
+
+void HaloEngine::set_grid(const GridInfo& g) {
+  for (int d = 0; d < NDIMS; ++d)
+    if (g.halowidths[d] < 1) fail("GridInfo: halo widths must be >= 1");
+  grid_ = g;
+  pool_.set_width(*std::max_element(g.halowidths.begin(), g.halowidths.end()));
 }
 
 void HaloEngine::debug_phase(hipStream_t stream, bool device, const char* phase) const {
@@ -259,38 +331,38 @@ void HaloEngine::exchange_dim_impl(const std::vector<Field>& fields, int dim, bo
   if (!has[0] && !has[1]) return;
   const int eb = fields[0].elem_bytes;
   const bool blit = device && pack_mode_[dim] == PackMode::Memcpy2D;
-  auto do_copies = [&](const std::vector<Copy2D>& cps) {
-    if (cps.empty()) return;
-    if (!device) return host_copy2d(cps, eb);
-    if (!blit) return launch_copy2d(cps, eb, stream);
+  const int64_t w = g.halowidths[dim];
+  auto do_copies = [&](const std::vector<Copy3D>& cps3) {
+    if (cps3.empty()) return;
+    std::vector<Copy2D> cps;
+    // (the blit alternative covers planes; slabs always use the kernel)
+    if (!device || !blit || !as_planes(cps3, cps)) return run_copies(cps3, eb, device, stream);
     std::vector<Copy2D> rest;
     for (const Copy2D& c : cps) {
       if (c.src_si != 1 || c.dst_si != 1) {
         rest.push_back(c);
         continue;
       }
-      const size_t w = static_cast<size_t>(c.n_inner) * eb;
-      const size_t sp = c.n_outer > 1 ? static_cast<size_t>(c.src_so) * eb : w;
-      const size_t dp = c.n_outer > 1 ? static_cast<size_t>(c.dst_so) * eb : w;
-      IGG_HIP_CHECK(hipMemcpy2DAsync(c.dst, dp, c.src, sp, w, static_cast<size_t>(c.n_outer),
+      const size_t rb = static_cast<size_t>(c.n_inner) * eb;
+      const size_t sp = c.n_outer > 1 ? static_cast<size_t>(c.src_so) * eb : rb;
+      const size_t dp = c.n_outer > 1 ? static_cast<size_t>(c.dst_so) * eb : rb;
+      IGG_HIP_CHECK(hipMemcpy2DAsync(c.dst, dp, c.src, sp, rb, static_cast<size_t>(c.n_outer),
                                      hipMemcpyDeviceToDevice, stream));
     }
     if (!rest.empty()) launch_copy2d(rest, eb, stream);
   };
 
   if (left == g.me && right == g.me) {
-    // Periodic with a single process along `dim`: in-place plane copies. The
-    // planes read (ol-1, size-ol) and written (0, size-1) are disjoint for every
-    // admissible overlap (periodic requires n >= 2*ol-1), so one launch suffices.
-    std::vector<Copy2D> cps;
+    // Periodic with a single process along `dim`: in-place slab copies. The
+    // planes read ([ol-w, ol), [size-ol, size-ol+w)) and written ([0, w),
+    // [size-w, size)) are disjoint for every admissible overlap and width
+    // (periodic requires n >= 2*ol-1, and ol >= 2w), so one launch suffices.
+    std::vector<Copy3D> cps;
     for (const Field& f : fields) {
       if (ol(g, dim, f) < 2) continue;
-      for (int s = 0; s < NNEIGHBORS; ++s) {
-        const Face src = face(f, dim, send_index(g, s, dim, f));
-        const Face dst = face(f, dim, recv_index(g, 1 - s, dim, f));
-        cps.push_back({src.base, dst.base, src.n_outer, src.n_inner, src.s_outer, src.s_inner,
-                       dst.s_outer, dst.s_inner});
-      }
+      for (int s = 0; s < NNEIGHBORS; ++s)
+        cps.push_back(move_copy(slab(f, dim, send_index(g, s, dim, f), w),
+                                slab(f, dim, recv_index(g, 1 - s, dim, f), w)));
     }
     do_copies(cps);
     return;
@@ -306,7 +378,7 @@ void HaloEngine::exchange_dim_impl(const std::vector<Field>& fields, int dim, bo
   if (!device && !transport_->host_capable())
     fail("update_halo: transport '", transport_->name(), "' cannot move host memory.");
 
-  std::vector<Copy2D> pack, unpack;
+  std::vector<Copy3D> pack, unpack;
   std::vector<P2POp> recvs, sends;
   // Receives: right side first, then left (update_halo.jl:47-49); sends: left
   // then right (:50-55). RCCL matches same-peer messages in issue order.
@@ -315,13 +387,11 @@ void HaloEngine::exchange_dim_impl(const std::vector<Field>& fields, int dim, bo
     for (size_t i = 0; i < fields.size(); ++i) {
       const Field& f = fields[i];
       if (ol(g, dim, f) < 2) continue;
-      const Face rf = face(f, dim, recv_index(g, s, dim, f));
+      const Face rf = slab(f, dim, recv_index(g, s, dim, f), w);
       char* ptr = rf.contiguous ? rf.base : pool_.recv(i, s, device);
       recvs.push_back({ptr, rf.bytes, static_cast<int>(g.neighbors[s][dim]),
                        static_cast<int>(i * 2 + s)});
-      if (!rf.contiguous)
-        unpack.push_back({ptr, rf.base, rf.n_outer, rf.n_inner, rf.n_inner, 1, rf.s_outer,
-                          rf.s_inner});
+      if (!rf.contiguous) unpack.push_back(unpack_copy(ptr, rf));
     }
   }
   for (int s = 0; s < NNEIGHBORS; ++s) {
@@ -329,11 +399,9 @@ void HaloEngine::exchange_dim_impl(const std::vector<Field>& fields, int dim, bo
     for (size_t i = 0; i < fields.size(); ++i) {
       const Field& f = fields[i];
       if (ol(g, dim, f) < 2) continue;
-      const Face sf = face(f, dim, send_index(g, s, dim, f));
+      const Face sf = slab(f, dim, send_index(g, s, dim, f), w);
       char* ptr = sf.contiguous ? sf.base : pool_.send(i, s, device);
-      if (!sf.contiguous)
-        pack.push_back({sf.base, ptr, sf.n_outer, sf.n_inner, sf.s_outer, sf.s_inner, sf.n_inner,
-                        1});
+      if (!sf.contiguous) pack.push_back(pack_copy(sf, ptr));
       // The receiver files this message under its opposite side.
       sends.push_back({ptr, sf.bytes, static_cast<int>(g.neighbors[s][dim]),
                        static_cast<int>(i * 2 + (1 - s))});
@@ -414,15 +482,18 @@ bool HaloEngine::dir_regions(const Field& f, int key, Region& rr, Region& sr) co
       const int64_t o = ol(g, d, f);
       // receive into my halo plane on side u_d; the matching send (direction
       // -u) reads my send plane on side -u_d.
-      rr.lo[d] = u[d] < 0 ? 0 : n - 1;
-      sr.lo[d] = u[d] < 0 ? n - o : o - 1;
-      rr.hi[d] = rr.lo[d] + 1;
-      sr.hi[d] = sr.lo[d] + 1;
+      const int64_t w = g.halowidths[d];
+      if (w > 1 && o < 2 * w) fail("Incoherent arguments: ol(A,dim)<2*halowidths[dim].");
+      rr.lo[d] = u[d] < 0 ? 0 : n - w;
+      sr.lo[d] = u[d] < 0 ? n - o : o - w;
+      rr.hi[d] = rr.lo[d] + w;
+      sr.hi[d] = sr.lo[d] + w;
     } else {
       // Exclude the halo planes that another message fills (neighbour exists).
       const bool act = active(f, d);
-      rr.lo[d] = sr.lo[d] = (act && g.neighbors[0][d] != PROC_NULL) ? 1 : 0;
-      rr.hi[d] = sr.hi[d] = (act && g.neighbors[1][d] != PROC_NULL) ? n - 1 : n;
+      const int64_t w = g.halowidths[d];
+      rr.lo[d] = sr.lo[d] = (act && g.neighbors[0][d] != PROC_NULL) ? w : 0;
+      rr.hi[d] = sr.hi[d] = (act && g.neighbors[1][d] != PROC_NULL) ? n - w : n;
     }
   }
   return rr.count() > 0;
@@ -452,7 +523,7 @@ void HaloEngine::exchange_put(const std::vector<Field>& fields, hipStream_t stre
     has_slot[key] = true;
     for (size_t i = 0; i < nf; ++i) {
       int64_t elems = 1;
-      for (int d = 0; d < NDIMS; ++d) elems *= u[d] != 0 ? 1 : fields[i].size[d];
+      for (int d = 0; d < NDIMS; ++d) elems *= u[d] != 0 ? g.halowidths[d] : fields[i].size[d];
       slot[key * nf + i] = per;
       per += static_cast<size_t>(round_up(elems * eb, static_cast<int64_t>(MSG_ALIGN)));
     }
@@ -462,7 +533,7 @@ void HaloEngine::exchange_put(const std::vector<Field>& fields, hipStream_t stre
   // kernels pick the half from the device-resident epoch.
   const int64_t half = static_cast<int64_t>(mesh.arena_bytes() / 2);
   const int me = mesh.rank();
-  std::vector<Copy2D> put, unpack;
+  std::vector<Copy3D> put, unpack;
   std::vector<int> out_ranks, in_ranks, nb_ranks;
   auto add = [](std::vector<int>& v, int r) {
     if (std::find(v.begin(), v.end(), r) == v.end()) v.push_back(r);
@@ -482,14 +553,12 @@ void HaloEngine::exchange_put(const std::vector<Field>& fields, hipStream_t stre
       const size_t off = slot[key * nf + i];
       if (to != PROC_NULL) {
         const Face sf = region_face(f, sr);
-        put.push_back({sf.base, mesh.arena(static_cast<int>(to)) + off, sf.n_outer, sf.n_inner, sf.s_outer,
-                       sf.s_inner, sf.n_inner, 1});
+        put.push_back(pack_copy(sf, mesh.arena(static_cast<int>(to)) + off));
         add(out_ranks, static_cast<int>(to));
       }
       if (from != PROC_NULL) {
         const Face rf = region_face(f, rr);
-        unpack.push_back({mesh.arena(me) + off, rf.base, rf.n_outer, rf.n_inner, rf.n_inner, 1, rf.s_outer,
-                          rf.s_inner});
+        unpack.push_back(unpack_copy(mesh.arena(me) + off, rf));
         add(in_ranks, static_cast<int>(from));
       }
     }
@@ -524,7 +593,7 @@ void HaloEngine::exchange_put(const std::vector<Field>& fields, hipStream_t stre
   prev_in_ = in_ranks;
   {
     TraceRange r("igg.put.pack");
-    launch_copy2d(put, eb, stream, /*system_fence=*/true, ParityShift{epoch, half, 1, 1});
+    run_copies(put, eb, true, stream, /*system_fence=*/true, ParityShift{epoch, half, 1, 1});
     debug_phase(stream, true, "igg.put.pack");
   }
   {
@@ -534,7 +603,7 @@ void HaloEngine::exchange_put(const std::vector<Field>& fields, hipStream_t stre
   }
   {
     TraceRange r("igg.put.unpack");
-    launch_copy2d(unpack, eb, stream, false, ParityShift{epoch, half, 2, 0});
+    run_copies(unpack, eb, true, stream, false, ParityShift{epoch, half, 2, 0});
     debug_phase(stream, true, "igg.put.unpack");
   }
   if (debug_sync_) mesh.check_error();  // a bounded wait of this exchange timed out
@@ -603,19 +672,16 @@ void HaloEngine::exchange_onephase(const std::vector<Field>& fields, bool device
   char* sbuf = send_bytes ? pool_.arena(0, send_bytes, device) : nullptr;
   char* rbuf = recv_bytes ? pool_.arena(1, recv_bytes, device) : nullptr;
   const int eb = fields[0].elem_bytes;
-  auto do_copies = [&](const std::vector<Copy2D>& cps) {
-    if (cps.empty()) return;
-    if (device) launch_copy2d(cps, eb, stream); else host_copy2d(cps, eb);
-  };
+  auto do_copies = [&](const std::vector<Copy3D>& cps) { run_copies(cps, eb, device, stream); };
   // 1. pack every non-zero-copy send region (one launch for all fields/directions)
-  std::vector<Copy2D> pack;
+  std::vector<Copy3D> pack;
   std::vector<P2POp> tsend, trecv;
   std::vector<const char*> self_src(27 * fields.size(), nullptr);
   for (const Msg& m : sends) {
     const Face& fc = m.face;
     char* dst = m.zero_copy ? fc.base : sbuf + m.off;
     if (!m.zero_copy)
-      pack.push_back({fc.base, dst, fc.n_outer, fc.n_inner, fc.s_outer, fc.s_inner, fc.n_inner, 1});
+      pack.push_back(pack_copy(fc, dst));
     if (m.peer == g.me) self_src[m.field * 27 + m.key] = dst;
     else tsend.push_back({dst, fc.bytes, static_cast<int>(m.peer), static_cast<int>(m.field * 27 + m.key)});
   }
@@ -625,7 +691,7 @@ void HaloEngine::exchange_onephase(const std::vector<Field>& fields, bool device
     debug_phase(stream, device, "igg.onephase.pack");
   }
   // 2. one communication phase for all remote messages
-  std::vector<Copy2D> unpack;
+  std::vector<Copy3D> unpack;
   for (const Msg& m : recvs) {
     const Face& fc = m.face;
     const char* src;
@@ -638,7 +704,7 @@ void HaloEngine::exchange_onephase(const std::vector<Field>& fields, bool device
       src = dst;
       if (m.zero_copy) continue;
     }
-    unpack.push_back({src, fc.base, fc.n_outer, fc.n_inner, fc.n_inner, 1, fc.s_outer, fc.s_inner});
+    unpack.push_back(unpack_copy(src, fc));
   }
   if (!tsend.empty() || !trecv.empty()) {
     TraceRange r("igg.onephase.transport");

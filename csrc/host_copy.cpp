@@ -150,4 +150,17 @@ void host_copy2d(const std::vector<Copy2D>& copies, int elem_bytes) {
   }
 }
 
+void host_copy3d(const std::vector<Copy3D>& copies, int elem_bytes) {
+  // A slab is n_outer independent 2-D copies of n_mid rows; they run through
+  // the 2-D path one after the other (each is threaded by its own size).
+  std::vector<Copy2D> planes;
+  for (const Copy3D& c : copies) {
+    if (c.n_outer * c.n_mid * c.n_inner <= 0) continue;
+    for (int64_t o = 0; o < c.n_outer; ++o)
+      planes.push_back({c.src + o * c.src_so * elem_bytes, c.dst + o * c.dst_so * elem_bytes, c.n_mid,
+                        c.n_inner, c.src_sm, c.src_si, c.dst_sm, c.dst_si});
+  }
+  host_copy2d(planes, elem_bytes);
+}
+
 }  // namespace igg

@@ -63,6 +63,30 @@ struct ParityShift {
   int add = 0;   // the half is ((*epoch + add) & 1)
 };
 
+// One strided 3-extent copy (a halo slab of w > 1 planes, a w x w x n edge, a
+// w^3 corner): n_outer x n_mid x n_inner elements, strides in elements.
+struct Copy3D {
+  const char* src;
+  char* dst;
+  int64_t n_outer, n_mid, n_inner;
+  int64_t src_so, src_sm, src_si;
+  int64_t dst_so, dst_sm, dst_si;
+};
+
+struct CopyBatch3 {
+  Copy3D c[MAX_BATCH];
+  int64_t block_start[MAX_BATCH + 1];
+  int n;
+  uint32_t flat_mask = 0;    // bit c: tiny region -> one element per lane over the flattened box
+  uint32_t gather_mask = 0;  // bit c: short unit-stride rows (the z slab of a C-ordered field): one row per lane
+  uint32_t vec_mask = 0;     // bit c (gather): a row is one aligned 4/8/16-B access on both sides
+  const uint64_t* epoch = nullptr;  // as CopyBatch
+  int64_t parity_bytes = 0;
+  int parity_side = 0;
+  int parity_add = 0;
+  CopyWait wait;
+};
+
 // Device: enqueue all copies (any count, split in MAX_BATCH chunks) on `stream`.
 // system_fence: every wave ends by waiting for its stores and writing its
 // XCD's L2 back at system scope (put transport: stores into a peer's
@@ -72,8 +96,15 @@ void launch_copy2d(const std::vector<Copy2D>& copies, int elem_bytes, hipStream_
                    bool system_fence = false, const ParityShift& parity = ParityShift{},
                    const CopyWait& wait = CopyWait{});
 
+// The same for 3-extent copies (wide halos), by the slab kernel; the arguments
+// mean what they mean for launch_copy2d.
+void launch_copy3d(const std::vector<Copy3D>& copies, int elem_bytes, hipStream_t stream,
+                   bool system_fence = false, const ParityShift& parity = ParityShift{},
+                   const CopyWait& wait = CopyWait{});
+
 // Host: perform all copies now (threaded above THREADCOPY_THRESHOLD bytes).
 void host_copy2d(const std::vector<Copy2D>& copies, int elem_bytes);
+void host_copy3d(const std::vector<Copy3D>& copies, int elem_bytes);
 
 // Host parallel-for on the runtime's persistent worker pool.
 void host_parallel_for(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)>& fn);

@@ -3,9 +3,11 @@
 // Reference behaviour reproduced (ImplicitGlobalGrid.jl):
 //   * ol(dim,A) = overlaps[dim] + size(A,dim) - nxyz[dim]; a field has a halo in
 //     `dim` iff ol >= 2 (src/shared.jl:94, src/update_halo.jl:370,429,809).
-//   * The halo is one plane per side whatever the overlap; send planes are
-//     ol-1 (left) and size-ol (right), receive planes 0 and size-1, 0-based
-//     (sendranges/recvranges, src/update_halo.jl:544-563).
+//   * The halo is w = halowidths[dim] planes per side (1 by default, whatever
+//     the overlap); with o = ol(dim,A) and n = size(A,dim) the send planes are
+//     [o-w, o) (left) and [n-o, n-o+w) (right), the receive planes [0, w) and
+//     [n-w, n), 0-based and half-open (sendranges/recvranges,
+//     src/update_halo.jl:544-563; w > 1 needs o >= 2w).
 //   * Dimensions are processed strictly x -> y -> z; each face spans the full
 //     extent of the other dimensions so edges/corners come out right without
 //     diagonal messages (src/update_halo.jl:40).
@@ -53,6 +55,7 @@ struct GridInfo {
   int64_t me = 0, nprocs = 1;
   Int3 nxyz{1, 1, 1};
   Int3 overlaps{2, 2, 2};
+  Int3 halowidths{1, 1, 1};
   std::array<Int3, NNEIGHBORS> neighbors{{{PROC_NULL, PROC_NULL, PROC_NULL},
                                           {PROC_NULL, PROC_NULL, PROC_NULL}}};
   // Rank at coords + disp*v for every direction v (dir_key order), PROC_NULL
@@ -81,12 +84,16 @@ enum class HaloMode : int { Sequential = 0, OnePhase = 1, Auto = 2 };
 //             contiguous on both sides; other faces still use the kernel.
 enum class PackMode : int { Kernel = 0, Memcpy2D = 1 };
 
-// A face (one plane of a field orthogonal to `dim`) as a strided 2-D region.
+// A face (one plane of a field orthogonal to `dim`) as a strided 2-D region;
+// with wide halos a slab of planes (or an edge / corner box) with a third
+// extent between the two (n_mid == 1 for a plane). The packed buffer order is
+// the memory order of the region: outer, mid, inner by decreasing stride.
 struct Face {
   char* base;
   int64_t n_outer, n_inner, s_outer, s_inner;
   bool contiguous;
   size_t bytes;
+  int64_t n_mid = 1, s_mid = 0;
 };
 
 // Half-open index box of a field.
@@ -95,14 +102,18 @@ struct Region {
   int64_t count() const { return (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]); }
 };
 
-// A box with at most two non-singleton extents as a strided 2-D region.
+// A box as a strided region (two extents where it has at most two
+// non-singleton ones, else three).
 Face region_face(const Field& f, const Region& r);
 
 int64_t ol(const GridInfo& g, int dim, const Field& f);
-int64_t max_halo_elems(const Field& f);
+int64_t max_halo_elems(const Field& f);  // of one plane
+// First plane of the send / receive range of `side` (halowidths[dim] planes).
 int64_t send_index(const GridInfo& g, int side, int dim, const Field& f);
 int64_t recv_index(const GridInfo& g, int side, int dim, const Field& f);
 Face face(const Field& f, int dim, int64_t index);
+// The planes [lo, lo + w) orthogonal to `dim`; face(f, dim, lo) for w == 1.
+Face slab(const Field& f, int dim, int64_t lo, int64_t w);
 
 // Grow-only per (field slot, side) send/recv byte buffers; separate host and
 // device pools (test hooks: capacities are observable).
@@ -110,6 +121,8 @@ class BufferPool {
  public:
   ~BufferPool();
   void ensure(const std::vector<Field>& fields, bool device);
+  // Planes per buffer (the grid's largest halo width).
+  void set_width(int64_t w) { width_ = w; }
   char* send(size_t slot, int side, bool device) const;
   char* recv(size_t slot, int side, bool device) const;
   size_t nslots(bool device) const { return (device ? dev_ : host_).size(); }
@@ -123,6 +136,7 @@ class BufferPool {
 
  private:
   bool frozen_ = false;
+  int64_t width_ = 1;
   struct Buf { char* p = nullptr; size_t bytes = 0; };
   struct Slot { Buf send[NNEIGHBORS], recv[NNEIGHBORS]; };
   void grow(Buf& b, size_t bytes, bool device);
@@ -143,7 +157,8 @@ class HaloEngine {
   std::shared_ptr<Transport> transport(bool device) const {
     return device ? dev_transport_ : host_transport_;
   }
-  GridInfo& grid() { return grid_; }
+  const GridInfo& grid() const { return grid_; }
+  void set_grid(const GridInfo& g);
   BufferPool& pool() { return pool_; }
 
   // Full update_halo! of `fields` (validated by the caller), stream-ordered.

@@ -205,4 +205,231 @@ void launch_copy2d(const std::vector<Copy2D>& copies, int elem_bytes, hipStream_
   else launch_sized<false>(copies, elem_bytes, stream, parity, wait);
 }
 
+// ------------------------------------------------------------ slab kernel
+//
+// Wide halos (halowidths > 1): a message is a slab of w planes, an edge of
+// w x w x n or a corner of w^3, i.e. a box with three extents. The case that
+// sets the cost is the z slab of a C-ordered field: nx*ny rows of w adjacent
+// elements, one cache line apart. Here a lane moves a whole row: one vector
+// access of w*sizeof(T) bytes when that is 4, 8 or 16 and both sides are
+// aligned to it (decided per copy on the host), scalar accesses otherwise. The
+// packed side is then w*sizeof(T) contiguous bytes per lane. Measured on a
+// 512^2 x 2 f64 slab this is as fast as two one-plane copies through the 2-D
+// kernel, not faster (16.0 against 15.5 us per pack + unpack pair: the second
+// plane's elements lie in lines the first plane's requests fetched,
+// profiles/wide_halo/NOTES.md); what the kernel buys is ONE region per message,
+// so a 26-direction exchange of a field still fits one launch.
+namespace {
+
+// GROWS rows (one per outer index) of one lane: all loads before the first store.
+template <typename V, bool FENCE>
+__device__ __forceinline__ void move_rows(const char* __restrict__ s, char* __restrict__ d, int64_t s_step,
+                                          int64_t d_step, int nr) {
+  // (rows past nr load row nr - 1 again, never stored: every v[k] is defined,
+  // which keeps the four instantiations of one kernel in 50 VGPRs; with
+  // predicated loads the register allocator needed 240)
+  V v[GROWS];
+#pragma unroll
+  for (int k = 0; k < GROWS; ++k)
+    v[k] = *reinterpret_cast<const V*>(s + (k < nr ? k : nr - 1) * s_step);
+#pragma unroll
+  for (int k = 0; k < GROWS; ++k)
+    if (k < nr) store<V, FENCE>(reinterpret_cast<V*>(d + k * d_step), v[k]);
+}
+
+template <typename T, bool FENCE>
+__global__ void __launch_bounds__(BLOCK) copy3d_batch_kernel(const CopyBatch3 batch) {
+  const int64_t b = blockIdx.x;
+  if (batch.wait.n > 0) {
+    // (CopyWait) as in copy2d_batch_kernel
+    if (threadIdx.x == 0) {
+      const uint64_t e = load_sys_relaxed(batch.wait.flags + PutFlags::EPOCH);
+      for (int k = 0; k < batch.wait.n; ++k)
+        spin_geq(batch.wait.flags + PutFlags::ARRIVED + batch.wait.rank[k], e, batch.wait.flags,
+                 batch.wait.timeout_ticks, 0x400 + k);
+    }
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  }
+  int c = 0;
+  while (c + 1 < batch.n && b >= batch.block_start[c + 1]) ++c;
+  const Copy3D& cp = batch.c[c];
+  const int64_t local = b - batch.block_start[c];
+  int64_t shift = 0;
+  if (batch.parity_side != 0) {
+    const uint64_t e = __hip_atomic_load(batch.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    shift = ((e + batch.parity_add) & 1) ? batch.parity_bytes : 0;
+  }
+  const char* sbase = cp.src + (batch.parity_side == 2 ? shift : 0);
+  char* dbase = cp.dst + (batch.parity_side == 1 ? shift : 0);
+  constexpr int64_t EB = sizeof(T);
+  if ((batch.flat_mask >> c) & 1u) {
+    // Edges, corners, narrow slabs: one element per lane over the flattened box.
+    const int64_t e = local * BLOCK + threadIdx.x;
+    const int64_t plane = cp.n_mid * cp.n_inner;
+    if (e < cp.n_outer * plane) {
+      const int64_t o = e / plane, r = e - o * plane;
+      const int64_t m = r / cp.n_inner, i = r - m * cp.n_inner;
+      store<T, FENCE>(reinterpret_cast<T*>(dbase) + o * cp.dst_so + m * cp.dst_sm + i * cp.dst_si,
+                      reinterpret_cast<const T*>(sbase)[o * cp.src_so + m * cp.src_sm + i * cp.src_si]);
+    }
+  } else if ((batch.gather_mask >> c) & 1u) {
+    // Short rows (n_inner < 64), many of them: a lane owns the row `m` of
+    // GROWS consecutive outer indices; a wave covers 64 consecutive rows, a
+    // workgroup 4 * GROWS outer indices.
+    const int64_t nmc = (cp.n_mid + 63) / 64;
+    const int64_t og = local / nmc, mc = local - og * nmc;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t m = mc * 64 + lane;
+    const int64_t o0 = (og * 4 + w) * GROWS;
+    if (m < cp.n_mid && o0 < cp.n_outer) {
+      const char* s = sbase + (o0 * cp.src_so + m * cp.src_sm) * EB;
+      char* d = dbase + (o0 * cp.dst_so + m * cp.dst_sm) * EB;
+      const int64_t ss = cp.src_so * EB, ds = cp.dst_so * EB;
+      const int nr = static_cast<int>(min<int64_t>(GROWS, cp.n_outer - o0));
+      const int rb = (batch.vec_mask >> c) & 1u ? static_cast<int>(cp.n_inner * EB) : 0;  // wave-uniform
+      if (rb == 16) {
+        move_rows<B16, FENCE>(s, d, ss, ds, nr);
+      } else if (rb == 8) {
+        move_rows<uint64_t, FENCE>(s, d, ss, ds, nr);
+      } else if (rb == 4) {
+        move_rows<uint32_t, FENCE>(s, d, ss, ds, nr);
+      } else {
+        // (not unrolled: the unrolled loop hoisted every load and took 240 VGPRs)
+#pragma unroll 1
+        for (int64_t i = 0; i < cp.n_inner; ++i)
+          move_rows<T, FENCE>(s + i * cp.src_si * EB, d + i * cp.dst_si * EB, ss, ds, nr);
+      }
+    }
+  } else {
+    // Long rows (x and y slabs of a C-ordered field collapse to these): a
+    // workgroup copies one CHUNK of one of the n_outer * n_mid rows.
+    const int64_t nchunks = (cp.n_inner + CHUNK - 1) / CHUNK;
+    const int64_t row = local / nchunks;
+    const int64_t i0 = (local - row * nchunks) * CHUNK;
+    const int64_t o = row / cp.n_mid, m = row - o * cp.n_mid;
+    const T* __restrict__ src = reinterpret_cast<const T*>(sbase) + o * cp.src_so + m * cp.src_sm;
+    T* __restrict__ dst = reinterpret_cast<T*>(dbase) + o * cp.dst_so + m * cp.dst_sm;
+    const int64_t n = cp.n_inner;
+    T v[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+      const int64_t i = i0 + k * BLOCK + threadIdx.x;
+      if (i < n) v[k] = src[i * cp.src_si];
+    }
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+      const int64_t i = i0 + k * BLOCK + threadIdx.x;
+      if (i < n) store<T, FENCE>(dst + i * cp.dst_si, v[k]);
+    }
+  }
+  if (FENCE) __builtin_amdgcn_s_waitcnt(0);  // as in copy2d_batch_kernel
+}
+
+// Merge extents that are adjacent in memory on both sides, then order the box
+// for the kernel's shapes. The element order of the copy does not change.
+Copy3D normalized(Copy3D c) {
+  if (c.n_mid > 1 && c.src_sm == c.n_inner * c.src_si && c.dst_sm == c.n_inner * c.dst_si) {
+    c.n_inner *= c.n_mid;
+    c.n_mid = 1;
+  } else if (c.n_inner == 1 && c.n_mid > 1) {
+    c.n_inner = c.n_mid, c.src_si = c.src_sm, c.dst_si = c.dst_sm;
+    c.n_mid = 1;
+  }
+  if (c.n_mid == 1) {
+    c.n_mid = c.n_outer, c.src_sm = c.src_so, c.dst_sm = c.dst_so;
+    c.n_outer = 1;
+  }
+  // (short rows keep n_outer when there are enough of them for a wave: the
+  // one-row-per-lane shape takes its GROWS independent loads from it)
+  if (c.n_outer > 1 && c.src_so == c.n_mid * c.src_sm && c.dst_so == c.n_mid * c.dst_sm &&
+      (c.n_inner >= 64 || c.n_mid < 64)) {
+    c.n_mid *= c.n_outer;
+    c.n_outer = 1;
+  }
+  // now the box is n_outer x n_mid rows of n_inner, n_outer > 1 only with n_mid > 1
+  if (c.n_outer == 1 && c.n_inner >= 64 && (c.src_si != 1 || c.dst_si != 1)) {
+    // long strided rows (a one-plane z face in a batch with slabs): one
+    // element per lane along the row, GROWS rows per lane
+    c.n_outer = c.n_mid, c.src_so = c.src_sm, c.dst_so = c.dst_sm;
+    c.n_mid = c.n_inner, c.src_sm = c.src_si, c.dst_sm = c.dst_si;
+    c.n_inner = 1;
+  }
+  if (c.n_outer == 1) c.src_so = c.dst_so = 0;
+  return c;
+}
+
+bool aligned_rows(const Copy3D& c, int eb, const ParityShift& par) {
+  const int64_t rb = c.n_inner * eb;
+  if (c.src_si != 1 || c.dst_si != 1 || (rb != 4 && rb != 8 && rb != 16)) return false;
+  if (par.side != 0 && par.bytes % rb != 0) return false;
+  auto ok = [&](const char* p, int64_t sm, int64_t so) {
+    return reinterpret_cast<uintptr_t>(p) % rb == 0 && (sm * eb) % rb == 0 && (so * eb) % rb == 0;
+  };
+  return ok(c.src, c.src_sm, c.src_so) && ok(c.dst, c.dst_sm, c.dst_so);
+}
+
+template <typename T, bool FENCE>
+void launch_typed3(const std::vector<Copy3D>& copies, hipStream_t stream, const ParityShift& par,
+                   const CopyWait& wait) {
+  size_t pos = 0;
+  while (pos < copies.size()) {
+    CopyBatch3 batch{};
+    batch.n = 0;
+    batch.epoch = par.epoch;
+    batch.parity_bytes = par.bytes;
+    batch.parity_side = par.side;
+    batch.parity_add = par.add;
+    batch.wait = wait;
+    int64_t blocks = 0;
+    while (pos < copies.size() && batch.n < MAX_BATCH) {
+      const Copy3D& in = copies[pos++];
+      const int64_t total = in.n_outer * in.n_mid * in.n_inner;
+      if (total <= 0) continue;
+      const Copy3D c = normalized(in);
+      const bool is_gather = c.n_inner < 64 && c.n_mid >= 64 && g_copy_gather;
+      const bool is_flat = !is_gather && c.n_inner < 64;
+      batch.c[batch.n] = c;
+      batch.block_start[batch.n] = blocks;
+      if (is_flat) batch.flat_mask |= 1u << batch.n;
+      if (is_gather) batch.gather_mask |= 1u << batch.n;
+      if (is_gather && aligned_rows(c, static_cast<int>(sizeof(T)), par)) batch.vec_mask |= 1u << batch.n;
+      blocks += is_flat     ? (total + BLOCK - 1) / BLOCK
+                : is_gather ? ((c.n_mid + 63) / 64) * ((c.n_outer + 4 * GROWS - 1) / (4 * GROWS))
+                            : c.n_outer * c.n_mid * ((c.n_inner + CHUNK - 1) / CHUNK);
+      ++batch.n;
+    }
+    if (batch.n == 0) continue;
+    batch.block_start[batch.n] = blocks;
+    if (blocks > 0x7fffffffLL) fail("launch_copy3d: too many blocks (", blocks, ")");
+    hipLaunchKernelGGL((copy3d_batch_kernel<T, FENCE>), dim3(static_cast<unsigned>(blocks)), dim3(BLOCK), 0,
+                       stream, batch);
+    IGG_HIP_CHECK(hipGetLastError());
+  }
+}
+
+template <bool FENCE>
+void launch_sized3(const std::vector<Copy3D>& copies, int elem_bytes, hipStream_t stream,
+                   const ParityShift& par, const CopyWait& wait) {
+  switch (elem_bytes) {
+    case 1: launch_typed3<uint8_t, FENCE>(copies, stream, par, wait); break;
+    case 2: launch_typed3<uint16_t, FENCE>(copies, stream, par, wait); break;
+    case 4: launch_typed3<uint32_t, FENCE>(copies, stream, par, wait); break;
+    case 8: launch_typed3<uint64_t, FENCE>(copies, stream, par, wait); break;
+    case 16: launch_typed3<B16, FENCE>(copies, stream, par, wait); break;
+    default: fail("launch_copy3d: unsupported element size ", elem_bytes, " bytes");
+  }
+}
+
+}  // namespace
+
+void launch_copy3d(const std::vector<Copy3D>& copies, int elem_bytes, hipStream_t stream,
+                   bool system_fence, const ParityShift& parity, const CopyWait& wait) {
+  if (copies.empty()) return;
+  if (wait.n < 0 || wait.n > 2 || (wait.n > 0 && !wait.flags)) fail("launch_copy3d: invalid CopyWait");
+  if (system_fence) launch_sized3<true>(copies, elem_bytes, stream, parity, wait);
+  else launch_sized3<false>(copies, elem_bytes, stream, parity, wait);
+}
+
 }  // namespace igg

@@ -75,14 +75,17 @@ class Diffusion3D:
     checkpoint.
 
     Two-step pass (``two_step``; IGG_STENCIL_TWOSTEP=auto|0|1): where nothing
-    looks at the field between steps and ``update_halo_`` has nothing to do -
-    ``run``/``capture`` on a GPU model without neighbours, periodic
-    self-exchange or loopback, not fused, not overlapped, no timer - pairs of
-    steps run as one kernel pass that reads T and Cp once and writes the field
-    two steps later (ops.stencil.diffusion3d_twostep_; bitwise the values of
-    two single steps). ``step``/``local_step`` stay single steps. ``variant``
-    names the single-step kernel: assigning another one than the selection ran
-    with switches the pass off until the original is assigned back.
+    looks at the field between steps and no halo is needed in between -
+    ``run``/``capture`` on a GPU model whose grid has a halo width of at least
+    2 in every dimension that ``update_halo_`` exchanges (a neighbour, a
+    periodic self-exchange, loopback; a grid without any is the trivial case),
+    not fused, not overlapped, no timer - pairs of steps run as one kernel pass
+    that reads T and Cp once and writes the field two steps later
+    (ops.stencil.diffusion3d_twostep_; bitwise the values of two single
+    steps), followed by ONE ``update_halo_`` of two planes per side.
+    ``step``/``local_step`` stay single steps. ``variant`` names the
+    single-step kernel: assigning another one than the selection ran with
+    switches the pass off until the original is assigned back.
 
     ``T2`` is the other ping-pong buffer: its boundary planes always equal
     ``T``'s fixed boundary values; its interior is the field of one step ago
@@ -185,10 +188,21 @@ class Diffusion3D:
                                                     - ((z - lz / 3.0) / 2) ** 2)
                                     + 50 * torch.exp(-((xs - lx / 2) / 2) ** 2 - ((y - ly / 2) / 2) ** 2
                                                      - ((z - lz / 1.5) / 2) ** 2))
+        if _wide_grid() and _exchanging():
+            # On a periodic grid the analytic values of T and Cp in the halo
+            # planes are not the images of the interior they overlap. A single
+            # step reads only T's plane 0 of them and the exchange rewrites what
+            # it computes there; the two-step pass computes its intermediate
+            # plane 1 from T's and Cp's own planes 0 .. 2, which must then be
+            # what the neighbour holds. So both forms start from exchanged halos
+            # (collective, like the variant autotune below; between the ranks of
+            # a non-periodic grid the values already agree).
+            update_halo_(self.T, self.Cp)
         self.T2.copy_(self.T)
-        sides = [[bool(gg.neighbors[0, d] != -1), bool(gg.neighbors[1, d] != -1)] for d in range(3)]
+        sides =[[bool(gg.neighbors[0, d] != -1), bool(gg.neighbors[1, d] != -1)] for d in range(3)]
         self.sides = sides
-        self.can_overlap = self.device.type == "cuda" and any(any(sd) for sd in sides)
+        # (the overlapped step's slabs and the fused exchange move one plane per side)
+        self.can_overlap = self.device.type == "cuda" and any(any(sd) for sd in sides) and not _wide_grid()
         self.inner = [stencil.inner_box(shape)]
         z_split = any(sides[2])
         if overlap and self.can_overlap and z_split and self.variant is None:
@@ -266,24 +280,31 @@ class Diffusion3D:
 
     def _two_step_now(self) -> bool:
         """Eligibility of the two-step pass right now: selected, GPU, the
-        plain step (not fused, not overlapped, no phase timer), update_halo_
-        would do nothing (no neighbour, periodic self-exchange or loopback on
-        any side of the grid as it is now), and the kernel has a form for the
-        shape."""
+        plain step (not fused, not overlapped, no phase timer), every
+        dimension update_halo_ exchanges on the grid as it is now (neighbour,
+        periodic self-exchange, loopback) has a halo at least two planes deep,
+        and the kernel has a form for the shape."""
         if not self.two_step or self.device.type != "cuda":
             return False
         if self.fused or self.overlap or self.timer is not None:
             return False
-        return _no_exchange() and stencil.twostep_ok(self.T, self.two_step_form)
+        return _pass_halo_ok() and stencil.twostep_ok(self.T, self.two_step_form)
 
     def _two_step_key(self):
         return (self.two_step_form, self.two_step_rounds) if self._two_step_now() else None
 
     def _pass(self) -> None:
-        """Two time steps in one pass (callers checked ``_two_step_now``)."""
+        """Two time steps in one pass (callers checked ``_two_step_now``), then
+        the exchange of the two halo planes per side the next pass reads. The
+        pass leaves planes 2 .. n-3 exact (the intermediate field's boundary
+        planes keep T's values), which includes the send planes [2, 4) and
+        [n-4, n-2); planes 0, 1, n-2, n-1 are what the exchange overwrites
+        (next to a physical boundary plane 0 is fixed, so plane 1 is exact)."""
         T, T2 = self.T, self.T2
         stencil.diffusion3d_twostep_(T2, T, self.Cp, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy, dz=self.dz,
                                      form=self.two_step_form, rounds=self.two_step_rounds, halo_z=HALO_Z)
+        if _exchanging():
+            update_halo_(T2)
         self.T, self.T2 = T2, T
         self._warm = True
 
@@ -292,13 +313,18 @@ class Diffusion3D:
         """Fused halo exchange possible: GPU, a neighbour, overlap 2 where split,
         n2 a multiple of 4 (vector kernels)."""
         gg = _grid.global_grid()
-        if self.device.type != "cuda" or not any(any(sd) for sd in self.sides):
+        if self.device.type != "cuda" or not any(any(sd) for sd in self.sides) or _wide_grid():
             return False
         if any(any(self.sides[d]) and int(gg.overlaps[d]) != 2 for d in range(3)):
             return False
         if gg.nprocs > 1 and not gg.comm.one_node:  # IPC peer mappings: one node only
             return False
         return int(self.T.shape[2]) % 4 == 0 and int(self.T.shape[2]) >= 8
+
+    def fused_available(self) -> bool:
+        """Whether ``set_fused(True)`` would switch the fused exchange on (never
+        on a grid with a halo width above 1: it moves one plane per side)."""
+        return self.can_fuse
 
     def set_fused(self, flag: bool) -> bool:
         """Switch the fused halo exchange on/off (collective: every rank at the
@@ -657,14 +683,24 @@ class Diffusion3D:
         return 3 * self.T.numel() * self.T.element_size()
 
 
-def _no_exchange() -> bool:
-    """update_halo_ would do nothing: the grid has no neighbour on any side
-    (a periodic single process and the loopback emulation are their own
-    neighbours and do exchange)."""
-    from ..parallel import halo as H
-
+def _exchanging() -> list:
+    """Dimensions in which update_halo_ moves anything on the grid as it is
+    now: a neighbour on either side (another rank, a periodic self-exchange,
+    the loopback emulation, which writes its sides into the neighbour table)."""
     gg = _grid.global_grid()
-    return not H.loopback_active() and all(int(gg.neighbors[s, d]) == -1 for s in range(2) for d in range(3))
+    return [d for d in range(3) if any(int(gg.neighbors[s, d]) != -1 for s in range(2))]
+
+
+def _pass_halo_ok() -> bool:
+    """The halo is deep enough for the two-step pass: at least two planes in
+    every exchanging dimension (a dimension exchanges on every rank or on
+    none, so all ranks agree)."""
+    gg = _grid.global_grid()
+    return all(int(gg.halowidths[d]) >= 2 for d in _exchanging())
+
+
+def _wide_grid() -> bool:
+    return any(int(w) > 1 for w in _grid.global_grid().halowidths)
 
 
 def _select_two_step(m: "Diffusion3D") -> None:
@@ -672,12 +708,16 @@ def _select_two_step(m: "Diffusion3D") -> None:
     1 on where eligible (form 0, library grid), auto (default): the chosen
     single-step kernel against every two-step form x GRID_ROUNDS in the time
     loop's ping-pong shape; the pass is kept only if its time PER STEP is
-    below the single-step kernel's."""
+    below the single-step kernel's. On a grid that exchanges, a single step is
+    kernel + update_halo_ and a pass is kernel + ONE update_halo_ for two
+    steps; the times are summed over the ranks (every rank must make the same
+    choice: one that exchanged every step would mismatch one that exchanges
+    every two), and the timing itself is collective."""
     env = os.environ.get("IGG_STENCIL_TWOSTEP", "auto").strip().lower()
     if env not in ("auto", "0", "1"):
         raise ValueError(f"IGG_STENCIL_TWOSTEP must be auto, 0 or 1, got {env!r}")
     m.two_step = False
-    if env == "0" or m.device.type != "cuda" or m.variant is None or not _no_exchange():
+    if env == "0" or m.device.type != "cuda" or m.variant is None or not _pass_halo_ok():
         return
     forms = [f for f in stencil.TWOSTEP_FORMS if stencil.twostep_ok(m.T, f)]
     if not forms:
@@ -689,8 +729,18 @@ def _select_two_step(m: "Diffusion3D") -> None:
     rd2 = [1.0 / m.dx ** 2, 1.0 / m.dy ** 2, 1.0 / m.dz ** 2]
     boxes = [(list(b[0]), list(b[1])) for b in m.inner]
     cands = [(f, r, HALO_Z) for f in forms for r in stencil.GRID_ROUNDS]
+    exchanging = bool(_exchanging())
     single, t = stencil.time_twostep_pingpong(m.T2, m.T, m.Cp, rd2, m.dt * m.lam, boxes,
-                                              (int(m.variant), int(m.rounds), bool(m.halo_z)), cands)
+                                              (int(m.variant), int(m.rounds), bool(m.halo_z)), cands,
+                                              exchange=update_halo_ if exchanging else None)
+    gg = _grid.global_grid()
+    if exchanging and gg.nprocs > 1:
+        import torch.distributed as dist
+
+        tot = torch.tensor([single] + [t[c] for c in cands], dtype=torch.float64)
+        dist.all_reduce(tot, group=gg.comm.gloo)
+        tot /= int(gg.nprocs)
+        single, t = float(tot[0]), {c: float(x) for c, x in zip(cands, tot[1:])}
     m.two_step_times = {"single": round(single, 5)}
     m.two_step_times.update({f"t{f}@r{r}": round(x, 5) for (f, r, _hz), x in t.items()})
     best = min(t, key=t.get)

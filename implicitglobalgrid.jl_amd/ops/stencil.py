@@ -232,13 +232,17 @@ def diffusion3d_twostep_(T2, T, Cp, *, lam: float, dt: float, dx: float, dy: flo
                                T.element_size(), int(form), s, int(rounds), bool(halo_z))
 
 
-def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, steps: int = 20, rounds: int = 5) -> tuple:
+def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, steps: int = 20, rounds: int = 5,
+                          exchange=None) -> tuple:
     """Median ms PER STEP of the single-step candidate ``single`` (a
     (variant, rounds, halo_z) triple) and of each two-step candidate (form,
     rounds, halo_z), interleaved, in the time loop's ping-pong shape on the
     model's own two buffers (``steps`` a multiple of 4: an even number of
-    passes). T is saved and restored; T2's interior is scribbled. Returns
-    (single ms, {candidate: ms})."""
+    passes). T is saved and restored; T2's interior is scribbled. With
+    ``exchange`` (``update_halo_`` on a grid whose halo is two planes deep) it
+    follows every kernel on the buffer just written, as in the time loop: one
+    exchange per step against one per pass (collective: every rank runs the
+    same candidates in the same order). Returns (single ms, {candidate: ms})."""
     n = list(T.shape)
     s = torch.cuda.current_stream()
     es = T.element_size()
@@ -251,12 +255,16 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
                 dst, src = (T2, T) if j % 2 == 0 else (T, T2)
                 native.diffusion3d(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, boxes, True,
                                    v, s.cuda_stream, gr, hz)
+                if exchange is not None:
+                    exchange(dst)
         else:
             f, gr, hz = c
             for j in range(k // 2):
                 dst, src = (T2, T) if j % 2 == 0 else (T, T2)
                 native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f,
                                            s.cuda_stream, gr, hz)
+                if exchange is not None:
+                    exchange(dst)
 
     order = [None] + list(candidates)
     times = {c: [] for c in order}

@@ -38,6 +38,7 @@ class GlobalGrid:
     nxyz: np.ndarray = field(default_factory=_i3)
     dims: np.ndarray = field(default_factory=_i3)
     overlaps: np.ndarray = field(default_factory=_i3)
+    halowidths: np.ndarray = field(default_factory=_i3)
     nprocs: int = -1
     me: int = -1
     coords: np.ndarray = field(default_factory=_i3)
@@ -60,7 +61,7 @@ class GlobalGrid:
         # get_global_grid() returns a deep copy of the data; runtime handles
         # (communicator, engine) are shared, not copied.
         out = copy.copy(self)
-        for k in ("nxyz_g", "nxyz", "dims", "overlaps", "coords", "neighbors", "periods"):
+        for k in ("nxyz_g", "nxyz", "dims", "overlaps", "halowidths", "coords", "neighbors", "periods"):
             setattr(out, k, getattr(self, k).copy())
         for k in ("cudaaware_MPI", "amdgpuaware_MPI", "loopvectorization"):
             setattr(out, k, list(getattr(self, k)))
@@ -164,6 +165,9 @@ def init_global_grid(
     overlapx: int = 2,
     overlapy: int = 2,
     overlapz: int = 2,
+    halowidthx: int = 1,
+    halowidthy: int = 1,
+    halowidthz: int = 1,
     disp: int = 1,
     reorder: int = 1,
     comm=None,
@@ -179,6 +183,14 @@ def init_global_grid(
     runtime (torch.distributed + RCCL) instead of MPI; ``comm`` may be a
     ``torch.distributed`` process group. ``reorder`` is accepted and ignored
     (ranks map row-major onto Cartesian coordinates).
+
+    ``halowidthx/y/z`` is the number of planes ``update_halo_`` moves per side
+    in that dimension (communication-avoiding steps: a halo ``w`` planes deep
+    lets a kernel advance ``w`` time steps per exchange). A width above 1 needs
+    an overlap of at least twice the width. The default is 1 in every
+    dimension; upstream ImplicitGlobalGrid defaults to ``max(1, overlap÷2)``.
+    This port differs so that grids with overlap 3 or 4 keep exchanging
+    exactly what they exchanged before the keyword existed.
     """
     if grid_is_initialized():
         raise IGGError("The global grid has already been initialized.")
@@ -186,6 +198,7 @@ def init_global_grid(
     dims = np.array([dimx, dimy, dimz], dtype=np.int64)
     periods = np.array([periodx, periody, periodz], dtype=np.int64)
     overlaps = np.array([overlapx, overlapy, overlapz], dtype=np.int64)
+    halowidths = np.array([halowidthx, halowidthy, halowidthz], dtype=np.int64)
     cudaaware = config.parse_aware_flags("CUDAAWARE_MPI")
     amdgpuaware = config.parse_aware_flags("ROCMAWARE_MPI")
     loopvect = config.parse_loopvectorization()
@@ -216,6 +229,13 @@ def init_global_grid(
             "Incoherent arguments: if nx, ny, or nz is smaller than 2*overlapx-1, 2*overlapy-1 or 2*overlapz-1, "
             "respectively, then the corresponding periodx, periody or periodz must not be set (or set 0)."
         )
+    if np.any(halowidths < 1):
+        raise IGGError("Invalid arguments: halowidthx, halowidthy and halowidthz must be greater than or equal to 1.")
+    if np.any((halowidths > 1) & (overlaps < 2 * halowidths)):
+        raise IGGError(
+            "Incoherent arguments: if halowidthx, halowidthy or halowidthz is greater than 1, then the corresponding "
+            "overlapx, overlapy or overlapz must be at least 2*halowidthx, 2*halowidthy or 2*halowidthz, respectively."
+        )
     dims[(nxyz == 1) & (dims == 0)] = 1
     owns = False
     if init_MPI:
@@ -235,7 +255,7 @@ def init_global_grid(
         nbrs[:, d] = native.cart_shift(me_, d, disp, dims.tolist(), periods.tolist())
     nxyz_g = dims * (nxyz - overlaps) + overlaps * (periods == 0)
     gg = GlobalGrid(
-        nxyz_g=nxyz_g, nxyz=nxyz, dims=dims, overlaps=overlaps, nprocs=nprocs, me=me_, coords=coords,
+        nxyz_g=nxyz_g, nxyz=nxyz, dims=dims, overlaps=overlaps, halowidths=halowidths, nprocs=nprocs, me=me_, coords=coords,
         neighbors=nbrs, periods=periods, disp=disp, reorder=reorder, comm=cm, cuda_enabled=cuda_en,
         amdgpu_enabled=amdgpu_en, cudaaware_MPI=cudaaware, amdgpuaware_MPI=amdgpuaware,
         loopvectorization=loopvect, quiet=quiet, owns_runtime=owns,

@@ -123,7 +123,7 @@ def peer_table(gg) -> list[int]:
 
 def _grid_info(gg) -> "native.GridInfo":
     return native.GridInfo(int(gg.me), int(gg.nprocs), gg.nxyz.tolist(), gg.overlaps.tolist(),
-                           gg.neighbors.tolist(), peer_table(gg))
+                           gg.neighbors.tolist(), peer_table(gg), gg.halowidths.tolist())
 
 
 HALO_MODES = {"sequential": 0, "onephase": 1, "auto": 2}
@@ -483,7 +483,8 @@ def enable_loopback(dims=(True, True, True)) -> None:
     for s_ in range(2):
         for d in range(NDIMS):
             gg.neighbors[s_, d] = nb[s_][d]
-    _engine.set_grid(native.GridInfo(1, 2, gg.nxyz.tolist(), gg.overlaps.tolist(), nb, peers))
+    _engine.set_grid(native.GridInfo(1, 2, gg.nxyz.tolist(), gg.overlaps.tolist(), nb, peers,
+                                     gg.halowidths.tolist()))
     _engine.set_transport(_loopback_comm, True)
     global _cur_transport
     _cur_transport = want
@@ -517,6 +518,15 @@ def _ol(gg, dim0: int, t: torch.Tensor) -> int:
     return int(gg.overlaps[dim0]) + s - int(gg.nxyz[dim0])
 
 
+def _check_width(gg, dim0: int, t: torch.Tensor) -> int:
+    """Halo width of ``t`` in ``dim0``; a field with a halo there (ol >= 2)
+    must overlap by at least twice the width."""
+    w = int(gg.halowidths[dim0])
+    if w > 1 and 2 <= _ol(gg, dim0, t) < 2 * w:
+        raise IGGError("Incoherent arguments: ol(A,dim)<2*halowidths[dim].")
+    return w
+
+
 def check_fields(*fields) -> None:
     gg = _grid.global_grid()
     for i, A in enumerate(fields):
@@ -527,6 +537,9 @@ def check_fields(*fields) -> None:
         raise IGGError(f"The fields at positions {_join(no_halo)} have no halo; remove them from the call.")
     if len(no_halo) > 0:
         raise IGGError(f"The field at position {no_halo[0]} has no halo; remove it from the call.")
+    for A in fields:
+        for d in range(A.dim()):
+            _check_width(gg, d, A)
     dups = [
         [i + 1, j + 1]
         for i in range(len(fields))
@@ -721,34 +734,41 @@ update_halo = update_halo_
 
 # --- ranges (update_halo.jl:544-563), 1-based like the reference --------------
 def sendranges(n: int, dim: int, A: torch.Tensor) -> list[range]:
-    """1-based index ranges of the plane of ``A`` sent to side ``n`` (1 left, 2 right) in ``dim``
-    (update_halo.jl:544-552)."""
+    """1-based index ranges of the planes of ``A`` sent to side ``n`` (1 left, 2 right) in ``dim``
+    (update_halo.jl:544-552): ``halowidths[dim]`` planes, 0-based ``[o-w, o)`` left and
+    ``[n-o, n-o+w)`` right."""
     gg = _grid.global_grid()
     o = _ol(gg, dim - 1, A)
     if o < 2:
         raise IGGError("Incoherent arguments: ol(A,dim)<2.")
+    w = _check_width(gg, dim - 1, A)
     size = [int(A.shape[d]) if A.dim() > d else 1 for d in range(NDIMS)]
-    i = size[dim - 1] - (o - 1) if n == 2 else 1 + (o - 1)
+    i = size[dim - 1] - (o - 1) if n == 2 else 1 + (o - w)
     r = [range(1, s + 1) for s in size]
-    r[dim - 1] = range(i, i + 1)
+    r[dim - 1] = range(i, i + w)
     return r
 
 
 def recvranges(n: int, dim: int, A: torch.Tensor) -> list[range]:
-    """1-based index ranges of the halo plane of ``A`` received from side ``n`` in ``dim``
-    (update_halo.jl:555-563)."""
+    """1-based index ranges of the halo planes of ``A`` received from side ``n`` in ``dim``
+    (update_halo.jl:555-563): 0-based ``[0, w)`` left and ``[n-w, n)`` right."""
     gg = _grid.global_grid()
     if _ol(gg, dim - 1, A) < 2:
         raise IGGError("Incoherent arguments: ol(A,dim)<2.")
+    w = _check_width(gg, dim - 1, A)
     size = [int(A.shape[d]) if A.dim() > d else 1 for d in range(NDIMS)]
-    i = size[dim - 1] if n == 2 else 1
+    i = size[dim - 1] - (w - 1) if n == 2 else 1
     r = [range(1, s + 1) for s in size]
-    r[dim - 1] = range(i, i + 1)
+    r[dim - 1] = range(i, i + w)
     return r
 
 
 def halosize(dim: int, A: torch.Tensor) -> tuple:
-    """Shape of the halo of ``A`` in ``dim`` (update_halo.jl:84)."""
+    """Shape of the halo of ``A`` in ``dim`` (update_halo.jl:84); with a halo
+    width above 1 it keeps ``dim`` with that extent."""
+    w = int(_grid.global_grid().halowidths[dim - 1]) if _grid.grid_is_initialized() else 1
+    if w > 1:
+        return tuple(w if d == dim - 1 else int(s) for d, s in enumerate(A.shape))
     if A.dim() > 1:
         return tuple(int(s) for d, s in enumerate(A.shape) if d != dim - 1)
     return (1,)
@@ -815,8 +835,8 @@ def halo_plan_summary(*fields) -> list[dict]:
                 if nb[s] == PROC_NULL:
                     continue
                 idx = native.send_index(_engine.grid, s, d, ft)
-                info = native.face_info(ft, d, idx)
-                entry["faces"].append({"field": i + 1, "side": s + 1, "bytes": info[6], "zero_copy": bool(info[5])})
+                info = native.slab_info(ft, d, idx, int(gg.halowidths[d]))
+                entry["faces"].append({"field": i + 1, "side": s + 1, "bytes": info[8], "zero_copy": bool(info[7])})
         out.append(entry)
     return out
 

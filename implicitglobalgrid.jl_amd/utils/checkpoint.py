@@ -36,6 +36,7 @@ def _grid_meta() -> dict:
         "nxyz": [int(v) for v in gg.nxyz],
         "nxyz_g": [int(v) for v in gg.nxyz_g],
         "overlaps": [int(v) for v in gg.overlaps],
+        "halowidths": [int(v) for v in gg.halowidths],
         "periods": [int(v) for v in gg.periods],
     }
 
@@ -106,7 +107,8 @@ def load_checkpoint(prefix: str, device=None) -> tuple[dict, dict]:
     if meta.get("format") != _FORMAT:
         raise IGGError(f"load_checkpoint: unsupported checkpoint format {meta.get('format')!r}")
     cur = _grid_meta()
-    for k in ("nprocs", "dims", "nxyz", "overlaps", "periods"):
+    meta.setdefault("halowidths", [1, 1, 1])  # written before halo widths existed: one plane per side
+    for k in ("nprocs", "dims", "nxyz", "overlaps", "halowidths", "periods"):
         if meta[k] != cur[k]:
             raise IGGError(f"load_checkpoint: checkpoint {k}={meta[k]} does not match the current grid ({cur[k]})")
     path = _rank_file(prefix, me)
