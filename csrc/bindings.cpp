@@ -750,6 +750,24 @@ PYBIND11_MODULE(_igg_native, m) {
       .def("flag", [](FusedAcoustic& f, int i) { return f.flag(i); }, py::arg("index"),
            "Word `index` of this rank's flag block (PutFlags: 0 EPOCH = completed steps, 2 COUNT).")
       .def("close", &FusedAcoustic::close);
+  // Two acoustic time steps in one pass (acoustic2_kernels.hip): GPU only.
+  m.def("acoustic2d_twostep",
+        [](uintptr_t p2, uintptr_t vx2, uintptr_t vy2, uintptr_t p, uintptr_t vx, uintptr_t vy, int64_t nx,
+           int64_t ny, double dtk, double dt_rho, double rdx, double rdy, int elem_bytes, int64_t chunk,
+           uintptr_t stream) {
+          TraceRange tr("igg.acoustic2d_twostep");
+          AcousticArgs a{p2, vx2, vy2, p, vx, vy, nx, ny, dtk, dt_rho, rdx, rdy, elem_bytes};
+          launch_acoustic2d_twostep(a, chunk, as_stream(stream));
+        },
+        py::arg("p2"), py::arg("vx2"), py::arg("vy2"), py::arg("p"), py::arg("vx"), py::arg("vy"), py::arg("nx"),
+        py::arg("ny"), py::arg("dtk"), py::arg("dt_rho"), py::arg("rdx"), py::arg("rdy"), py::arg("elem_bytes"),
+        py::arg("chunk") = 0, py::arg("stream") = 0);
+  m.def("acoustic2d_twostep_ok",
+        [](int64_t nx, int64_t ny, int elem_bytes) {
+          AcousticArgs a{0, 0, 0, 0, 0, 0, nx, ny, 0.0, 0.0, 1.0, 1.0, elem_bytes};
+          return acoustic2d_twostep_ok(a);
+        },
+        py::arg("nx"), py::arg("ny"), py::arg("elem_bytes"));
   m.def("acoustic2d_set_variant", &acoustic2d_set_variant);
   m.def("acoustic2d_set_chunk", &acoustic2d_set_chunk);
   m.def("diffusion3d_set_rounds", &diffusion3d_set_rounds);

@@ -60,6 +60,21 @@ void acoustic2d_set_variant(int v);
 void acoustic2d_set_chunk(int64_t rows);  // rows of i per wave of the marching kernel
 void host_acoustic2d(const AcousticArgs& a);
 
+// Two time steps in one pass (kernels/acoustic2_kernels.hip), for a rank whose
+// fields nobody reads or exchanges between the two steps: P2, Vx2, Vy2 receive,
+// bitwise, what two launches of the vector-march kernel leave (ping-pong
+// through a temporary), every element of them is written, and P, Vx, Vy are
+// only read; the intermediate step stays in registers. The boundary faces (Vx
+// faces 0 / nx, Vy faces 0 / ny) keep their input values through both steps:
+// the rule lives in the kernel. `chunk`: rows of x written per wave (0: the
+// default; any value >= 1 is legal); a chunk re-reads two rows of lead-in.
+// Fails before any launch where acoustic2d_twostep_ok is false or an output
+// pointer equals an input pointer.
+void launch_acoustic2d_twostep(const AcousticArgs& a, int64_t chunk, hipStream_t stream);
+// The vector kernel's shape rule: element size 4 or 8, ny a multiple of the
+// 16-byte vector (VJ = 4 / 2) and >= 2 * VJ, nx >= 1.
+bool acoustic2d_twostep_ok(const AcousticArgs& a);
+
 // Fused halo exchange of Acoustic2D, the counterpart of FusedHalo (fused.hpp)
 // for the 2-D staggered step. update_halo!(Vx2, Vy2) (reference semantics,
 // src/update_halo.jl:32-78) would overwrite Vx2's x-halo faces and y-halo

@@ -20,27 +20,56 @@ and one 1-wave sync kernel completes the step; every other halo value is
 recomputed locally with the same arithmetic, so the fields are bitwise equal to
 the update_halo_ path (tests/test_acoustic.py) - the communication is hidden
 inside the HBM-bound sweep instead of following it.
+
+Two-step pass (``two_step``; IGG_ACOUSTIC_TWOSTEP=auto|0|1): on a rank without
+neighbours nobody looks at the fields between two steps (``update_halo_`` is a
+no-op there), so ``run``/``capture`` advance pairs of steps with one kernel pass
+(csrc/kernels/acoustic2_kernels.hip) that reads P, Vx, Vy once and writes the
+fields two steps later, bitwise equal to two single steps.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
 from .. import parallel  # noqa: F401
 from .._native import native
+from ..ops import stencil as _stencil
 from ..parallel import grid as _grid
 from ..parallel.halo import capture_graph, update_halo_
 from ..utils import placement as _placement
-from .diffusion3d import GRAPH_STEPS
+from .diffusion3d import GRAPH_STEPS, TWOSTEP_GRAPH_STEPS
 from ..utils.tools import coords_g, nx_g, ny_g
+
+# Chunk sizes (rows of x written per wave) the selection times the two-step
+# pass with. A chunk re-reads two rows of lead-in (2/chunk more input), a
+# short one puts more waves in flight: 4 .. 12 lie within a few per cent of
+# each other at 8192^2 f32 and 4096^2 f64, 1 .. 2 and 64+ are slower
+# (profiles/acoustic_twostep/NOTES.md).
+TWOSTEP_CHUNKS = (4, 8, 12, 16, 32)
 
 
 class Acoustic2D:
     """2-D staggered acoustic wave propagation (pressure P at cell centres,
     velocities Vx/Vy on staggered faces: nx+1 / ny+1) with one fused HIP kernel
     per step and one ``update_halo_(Vx2, Vy2)`` (mixed overlaps); the 2-D
-    staggered config of BASELINE.json."""
+    staggered config of BASELINE.json.
+
+    Two-step pass (``two_step``; IGG_ACOUSTIC_TWOSTEP=auto|0|1): in ``run`` and
+    ``capture`` of a GPU model on a grid without any neighbour (no other rank,
+    no periodic self-exchange, no loopback), not fused, pairs of steps run as
+    one kernel pass that reads P, Vx, Vy once and writes the fields two steps
+    later (ops.stencil.acoustic2d_twostep_; bitwise the values of two single
+    steps). ``auto`` (default) times the single-step kernel against the pass
+    with the chunks of ``TWOSTEP_CHUNKS`` on the model's own buffers and keeps
+    the pass only if its time per step is lower (``two_step_times``,
+    ``two_step_chunk``). ``step``/``local_step`` stay single steps.
+
+    ``P2``/``Vx2``/``Vy2`` are the other ping-pong buffers: the state of one
+    step ago after a single step and of TWO steps ago after a two-step pass
+    (whatever runs next rewrites them either way)."""
 
     def __init__(self, *, dtype=torch.float32, device=None, K: float = 1.0, rho: float = 1.0,
                  lx: float = 10.0, ly: float = 10.0):
@@ -99,6 +128,38 @@ class Acoustic2D:
         # remote stores must not overtake this rank's own writes to the fields
         # (switch into fused mode, restore, external edits: mark_modified).
         self._entry = True
+        # Two-step pass: whether the selection kept it, its chunk (0: the
+        # kernel's default), the A/B's ms per step ("single", "c<chunk>") and
+        # the pass setting the graph was captured with (None: single steps).
+        self.two_step = False
+        self.two_step_chunk = 0
+        self.two_step_times = {}
+        self._graph_two = None
+        _select_two_step(self)
+
+    def _two_step_now(self) -> bool:
+        """Eligibility of the two-step pass right now: selected, GPU, not
+        fused, no neighbour of any kind in x or y on the grid as it is now,
+        and the kernel takes the shape."""
+        if not self.two_step or self.device.type != "cuda" or self.fused:
+            return False
+        return _no_neighbours() and _stencil.acoustic2d_twostep_ok(self.P)
+
+    def _two_step_key(self):
+        return int(self.two_step_chunk) if self._two_step_now() else None
+
+    def _pass(self) -> None:
+        """Two time steps in one pass (callers checked ``_two_step_now``: no
+        exchange is due). One swap of the buffer roles."""
+        s = torch.cuda.current_stream().cuda_stream
+        native.acoustic2d_twostep(self.P2.data_ptr(), self.Vx2.data_ptr(), self.Vy2.data_ptr(), self.P.data_ptr(),
+                                  self.Vx.data_ptr(), self.Vy.data_ptr(), self.nx, self.ny, self.dt * self.K,
+                                  self.dt / self.rho, 1.0 / self.dx, 1.0 / self.dy, self.P.element_size(),
+                                  int(self.two_step_chunk), s)
+        self.P, self.P2 = self.P2, self.P
+        self.Vx, self.Vx2 = self.Vx2, self.Vx
+        self.Vy, self.Vy2 = self.Vy2, self.Vy
+        self._warm = True
 
     def _time_placements(self, cands) -> list:
         """ms per step of this model's kernel on each candidate carve
@@ -231,18 +292,29 @@ class Acoustic2D:
         self.Vx, self.Vx2 = self.Vx2, self.Vx
         self.Vy, self.Vy2 = self.Vy2, self.Vy
 
-    def capture(self, steps: int = GRAPH_STEPS) -> None:
-        """hipGraph of ``steps`` (even) time steps: buffers are back in their
+    def capture(self, steps: int = None) -> None:
+        """hipGraph of ``steps`` (even; default GRAPH_STEPS, TWOSTEP_GRAPH_STEPS
+        while the two-step pass is on) time steps: buffers are back in their
         roles after a replay; replay launch overhead (~9 us on MI355X) is paid
-        once per ``steps``."""
+        once per ``steps``. With the two-step pass an even number of PASSES is
+        recorded (``steps // 4 * 2``), closed by ``steps % 4`` single steps."""
         if self.device.type != "cuda":
             raise RuntimeError("Acoustic2D.capture: hipGraphs need a GPU model")
+        two = self._two_step_key()
+        if steps is None:
+            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
+        steps = int(steps)
         if steps < 2 or steps % 2:
             raise ValueError("Acoustic2D.capture: steps must be even and >= 2")
         if not self._warm or (self.fused and self._entry):
             self.step()  # the graph holds steady-state steps only (no entry barrier)
         def record():
-            for _ in range(steps):
+            singles = steps
+            if two is not None:
+                singles = steps % 4
+                for _ in range(steps // 4 * 2):
+                    self._pass()
+            for _ in range(singles):
                 self._step()  # no exit barrier inside the graph: run() drains once
 
         self.graph = None
@@ -251,12 +323,14 @@ class Acoustic2D:
         self.graph = g
         self.graph_steps = steps
         self._graph_P = self.P.data_ptr()
+        self._graph_two = two
 
     def run(self, nt: int) -> None:
         """Advance ``nt`` steps (graph replays where captured); one exit barrier
         at the end in fused mode (``_drain``), none between the steps."""
         ran = nt > 0
-        if self.graph is not None:
+        two = self._two_step_key()
+        if self.graph is not None and self._graph_two == two:
             # The captured steps read the capture's P/Vx/Vy first and hold no
             # entry barrier: one eager step realigns an odd step count or
             # performs a pending barrier (mark_modified, restore).
@@ -266,6 +340,10 @@ class Acoustic2D:
             for _ in range(nt // self.graph_steps):
                 self.graph.replay()
             nt %= self.graph_steps
+        if two is not None:
+            for _ in range(nt // 2):
+                self._pass()
+            nt %= 2
         for _ in range(nt):
             self._step()
         if ran:
@@ -275,7 +353,9 @@ class Acoustic2D:
         return self.P.data_ptr() == self._graph_P and not (self.fused and self._entry)
 
     def save(self, prefix: str, step: int = 0) -> str:
-        """Per-rank checkpoint of the model state (collective; utils.checkpoint)."""
+        """Per-rank checkpoint of the model state (collective; utils.checkpoint).
+        P2/Vx2/Vy2 are saved as they are: the state of one step ago, or of two
+        steps ago if a two-step pass ran last (the next step rewrites them)."""
         from ..utils.checkpoint import save_checkpoint
 
         return save_checkpoint(prefix, step=step, P=self.P, Vx=self.Vx, Vy=self.Vy, P2=self.P2, Vx2=self.Vx2,
@@ -298,8 +378,58 @@ class Acoustic2D:
 
     @property
     def a_eff_bytes(self) -> int:
-        """Each of P, Vx, Vy read once and written once per step."""
+        """Each of P, Vx, Vy read once and written once per step. The two-step
+        pass moves about half of that, so T_eff = a_eff_bytes / t_it can exceed
+        the HBM bandwidth while it is on."""
         return 2 * (self.P.numel() + self.Vx.numel() + self.Vy.numel()) * self.P.element_size()
+
+
+def _no_neighbours() -> bool:
+    """No entry of the grid's neighbour table in x or y: no other rank, no
+    periodic self-exchange, no loopback emulation (update_halo_ is a no-op)."""
+    gg = _grid.global_grid()
+    return all(int(gg.neighbors[s, d]) == -1 for s in range(2) for d in range(2))
+
+
+def _select_two_step(m: "Acoustic2D") -> None:
+    """Decide the two-step pass for this model (IGG_ACOUSTIC_TWOSTEP): 0 off,
+    1 on where eligible (the kernel's default chunk), auto (default): the
+    single-step kernel against the pass with every chunk of TWOSTEP_CHUNKS, on
+    the model's own six buffers in the time loop's ping-pong shape,
+    interleaved rounds, medians; the pass is kept only if its time PER STEP is
+    lower. The fields are put back into their initial state afterwards."""
+    env = os.environ.get("IGG_ACOUSTIC_TWOSTEP", "auto").strip().lower()
+    if env not in ("auto", "0", "1"):
+        raise ValueError(f"IGG_ACOUSTIC_TWOSTEP must be auto, 0 or 1, got {env!r}")
+    m.two_step, m.two_step_chunk, m.two_step_times = False, 0, {}
+    if env == "0" or m.device.type != "cuda" or not _no_neighbours() or not _stencil.acoustic2d_twostep_ok(m.P):
+        return
+    if env == "1":
+        m.two_step = True
+        return
+    a, b = (m.P, m.Vx, m.Vy), (m.P2, m.Vx2, m.Vy2)
+    backup = [t.clone() for t in a + b]
+    s = torch.cuda.current_stream().cuda_stream
+    coef = (m.nx, m.ny, m.dt * m.K, m.dt / m.rho, 1.0 / m.dx, 1.0 / m.dy, m.P.element_size())
+
+    def ptrs(dst, src):
+        return [t.data_ptr() for t in dst + src]
+
+    try:
+        single, t = _stencil.time_acoustic_twostep_pingpong(
+            a, b, lambda dst, src: native.acoustic2d(*ptrs(dst, src), *coef, True, s),
+            lambda dst, src, c: native.acoustic2d_twostep(*ptrs(dst, src), *coef, int(c), s), TWOSTEP_CHUNKS)
+    finally:
+        for dst, src in zip(a + b, backup):
+            dst.copy_(src)
+        torch.cuda.synchronize()
+        del backup
+    m.two_step_times = {"single": round(single, 5)}
+    m.two_step_times.update({f"c{c}": round(x, 5) for c, x in t.items()})
+    best = min(t, key=t.get)
+    if t[best] < single:
+        m.two_step_chunk = int(best)
+        m.two_step = True
 
 
 def _carve_fine(tensors, split: bool = False):

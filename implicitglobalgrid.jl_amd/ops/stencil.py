@@ -287,6 +287,93 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
     return med.pop(None), med
 
 
+def _acoustic_shapes_ok(P, Vx, Vy) -> bool:
+    if P.dim() != 2:
+        return False
+    nx, ny = int(P.shape[0]), int(P.shape[1])
+    return tuple(Vx.shape) == (nx + 1, ny) and tuple(Vy.shape) == (nx, ny + 1)
+
+
+def acoustic2d_twostep_ok(P) -> bool:
+    """Whether the two-step acoustic pass can run on pressure field ``P`` (GPU,
+    float32/float64, 2-D contiguous (nx, ny), ny a multiple of the 16-byte
+    vector and at least two vectors: the vector kernel's own rule)."""
+    if not (P.is_cuda and P.dim() == 2 and P.is_contiguous() and P.dtype in (torch.float32, torch.float64)):
+        return False
+    return bool(native.acoustic2d_twostep_ok(int(P.shape[0]), int(P.shape[1]), P.element_size()))
+
+
+def acoustic2d_twostep_(P2, Vx2, Vy2, P, Vx, Vy, *, dt: float, K: float, rho: float, dx: float, dy: float,
+                        chunk: int = 0, stream: int | None = None) -> None:
+    """Two acoustic time steps in one pass over memory
+    (csrc/kernels/acoustic2_kernels.hip): afterwards ``P2``, ``Vx2``, ``Vy2``
+    hold, bitwise, what two launches of the single-step kernel leave (ping-pong
+    through a temporary, no halo exchange in between). Every element of the
+    outputs is written; the boundary faces (Vx faces 0 / nx, Vy faces 0 / ny)
+    keep their input values. ``P`` (nx, ny), ``Vx`` (nx+1, ny), ``Vy``
+    (nx, ny+1) are only read. ``chunk``: rows of x written per wave (0: the
+    kernel's default; each chunk re-reads two rows of lead-in). GPU only;
+    raises ``IGGError`` without launching for CPU, non-contiguous, mis-shaped,
+    mixed-dtype or aliasing tensors and where ``acoustic2d_twostep_ok`` is
+    false."""
+    ins, outs = (("P", P), ("Vx", Vx), ("Vy", Vy)), (("P2", P2), ("Vx2", Vx2), ("Vy2", Vy2))
+    for name, A in ins + outs:
+        if not A.is_cuda:
+            raise IGGError(f"acoustic2d_twostep: {name} is not a GPU tensor (there is no host two-step kernel)")
+        if not A.is_contiguous():
+            raise IGGError(f"acoustic2d_twostep: {name} must be C-contiguous")
+        if A.dtype != P.dtype or A.device != P.device:
+            raise IGGError("acoustic2d_twostep: all six fields must have one dtype and device")
+    if not (_acoustic_shapes_ok(P, Vx, Vy) and _acoustic_shapes_ok(P2, Vx2, Vy2) and P2.shape == P.shape):
+        raise IGGError("acoustic2d_twostep: shapes must be P (nx, ny), Vx (nx+1, ny), Vy (nx, ny+1), inputs and "
+                       f"outputs alike (got {[tuple(A.shape) for _n, A in ins + outs]})")
+    if any(o.data_ptr() == i.data_ptr() for _n, o in outs for _m, i in ins):
+        raise IGGError("acoustic2d_twostep: an output aliases an input (use ping-pong buffers)")
+    if not acoustic2d_twostep_ok(P):
+        raise IGGError(f"acoustic2d_twostep: cannot run shape {tuple(P.shape)} {P.dtype}")
+    if int(chunk) < 0:
+        raise IGGError(f"acoustic2d_twostep: chunk must be >= 0, got {chunk}")
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    native.acoustic2d_twostep(P2.data_ptr(), Vx2.data_ptr(), Vy2.data_ptr(), P.data_ptr(), Vx.data_ptr(),
+                              Vy.data_ptr(), int(P.shape[0]), int(P.shape[1]), dt * K, dt / rho, 1.0 / dx, 1.0 / dy,
+                              P.element_size(), int(chunk), s)
+
+
+def time_acoustic_twostep_pingpong(a, b, launch_single, launch_pass, chunks, steps: int = 20,
+                                   rounds: int = 5) -> tuple:
+    """Median ms PER STEP of the single-step acoustic kernel and of the
+    two-step pass with each chunk of ``chunks``, interleaved, in the time
+    loop's ping-pong shape between the field triples ``a`` and ``b`` (``steps``
+    a multiple of 4: an even number of passes). ``launch_single(dst, src)`` /
+    ``launch_pass(dst, src, chunk)`` launch on the current stream. Both triples
+    are scribbled (callers restore them). Returns (single ms, {chunk: ms})."""
+    s = torch.cuda.current_stream()
+
+    def run(c, k):
+        n = k if c is None else k // 2
+        for j in range(n):
+            dst, src = (b, a) if j % 2 == 0 else (a, b)
+            if c is None:
+                launch_single(dst, src)
+            else:
+                launch_pass(dst, src, c)
+
+    order = [None] + list(chunks)
+    times = {c: [] for c in order}
+    for c in order:
+        run(c, 4)
+    for _ in range(rounds):
+        for c in order:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            run(c, steps)
+            e1.record(s)
+            e1.synchronize()
+            times[c].append(e0.elapsed_time(e1) / steps)
+    med = {c: sorted(t)[len(t) // 2] for c, t in times.items()}
+    return med.pop(None), med
+
+
 def diffusion3d_reference(T, Cp, *, lam, dt, dx, dy, dz) -> torch.Tensor:
     """Plain-PyTorch (fp64) reference of the reference example's 5 broadcasts."""
     T = T.double()

@@ -22,7 +22,8 @@ nodes; parallel/transport_select.py); ``put`` = one-sided IPC stores over xGMI
 (one node); ``rccl`` = grouped ncclSend/ncclRecv; ``staged`` = host-staged
 gloo, the reference's non-GPU-aware path. Also ``IGG_STENCIL_VARIANT`` (int or
 ``auto``), ``IGG_STENCIL_TWOSTEP`` (``auto`` | ``0`` | ``1``: the diffusion model's
-two-steps-per-pass kernel on a rank without neighbours), ``IGG_DEBUG_SYNC`` (synchronise after every halo update), ``IGG_QUIET``.
+two-steps-per-pass kernel on a rank without neighbours),
+``IGG_ACOUSTIC_TWOSTEP`` (the same for the acoustic model), ``IGG_DEBUG_SYNC`` (synchronise after every halo update), ``IGG_QUIET``.
 """
 from __future__ import annotations
 
