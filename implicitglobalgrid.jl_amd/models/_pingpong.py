@@ -1,0 +1,241 @@
+"""The time loop the models share: ping-pong buffers advanced by single steps,
+two-step passes and hipGraph replays (``PingPongModel``), and what the models
+read off the grid to set it up (exchanging dimensions, the fused exchange's
+peer mesh, the two-step selection's bookkeeping).
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+
+from .._native import native
+from ..parallel import grid as _grid
+from ..parallel.halo import capture_graph
+
+# Time steps per captured hipGraph (even): one replay launch (~9 us) per
+# GRAPH_STEPS steps instead of per 2 (profiles/r1_fused/graph_gaps.txt).
+GRAPH_STEPS = 10
+# While the two-step pass is on a graph holds passes, and an even number of
+# them hands the ping-pong buffers back in their roles: 20 steps = 10 passes.
+TWOSTEP_GRAPH_STEPS = 20
+
+
+class PingPongModel:
+    """``step``/``run``/``capture`` and ``save``/``restore`` of a model that
+    advances ping-pong buffers. A model supplies:
+
+    * ``_step()`` / ``_pass()``: the launches of one time step / of one
+      two-step pass, each ending in ``_swap()`` (exchange the buffer roles)
+      and ``_warm = True``;
+    * ``_two_step_now()``: whether ``run``/``capture`` may use the pass right
+      now, and ``_pass_key()``: the pass's setting (what a graph of passes
+      bakes in; never None);
+    * ``_capture_start()``: bring the model into the state a capture may start
+      from and note what ``_graph_ready()`` compares; ``_graph_ready()``:
+      whether the model is in that state again (a replay may start);
+    * optionally ``_capture_cfg()`` (further settings a graph bakes in) and
+      ``_replayed(k)`` (bookkeeping after ``k`` replayed steps);
+    * ``_fused_handle``: the native fused exchange (None before the first
+      ``set_fused(True)``), ``fused``, ``device``;
+    * ``_fields``: the checkpointed attributes in file order, ``sync_halo()``
+      and ``mark_modified()``.
+    """
+
+    _fields = ()
+
+    def __init__(self):
+        self.graph = None
+        self.graph_steps = 2
+        self._warm = False  # an eager step ran (halo buffers, plan cache, kernel variant are set up)
+        self._graph_two = None  # pass key of the capture, None: single steps
+        self._graph_cfg = None  # _capture_cfg() of the capture
+
+    def _two_step_key(self):
+        return self._pass_key() if self._two_step_now() else None
+
+    def _capture_cfg(self):
+        return None
+
+    def _replayed(self, k: int) -> None:
+        pass
+
+    def step(self) -> None:
+        """Advance one time step (buffer swap included). In fused mode the
+        neighbours' stores of this step into this rank's memory precede later
+        work on the stream (``_drain``)."""
+        self._step()
+        self._drain()
+
+    def _drain(self) -> None:
+        """Exit barrier of in-kernel synchronised fused steps (collective): the
+        last step's neighbour stores into this rank's arena and fields are
+        complete before anything queued after it touches them (sync_halo, a
+        restore, a comparison, gather_, a mode switch). No-op after a
+        sync-kernel step."""
+        if self.fused:
+            self._fused_handle.drain(torch.cuda.current_stream().cuda_stream)
+
+    def clear_error(self) -> None:
+        """Reset the fused exchange's sticky timeout word on this rank (after
+        a failed fused step was handled, e.g. the fused exchange was dropped)."""
+        if self._fused_handle is not None:
+            self._fused_handle.clear_error()
+
+    def check(self) -> None:
+        """Raise if a fused-exchange sync kernel timed out waiting for a neighbour."""
+        if self._fused_handle is not None:
+            self._fused_handle.check_error()
+
+    def capture(self, steps: int = None) -> None:
+        """Record ``steps`` (even, default GRAPH_STEPS; TWOSTEP_GRAPH_STEPS
+        while the two-step pass is on) time steps in a hipGraph for ``run``.
+
+        A step is a chain of launches (stencil, pack, RCCL group, unpack per
+        dimension; or fused stencil + sync) whose gaps are host launch latency;
+        replaying a graph removes that latency, and a graph replay costs ~9 us
+        to launch on MI355X (profiles/r1_fused/), so several steps are captured
+        per graph. An even count puts the ping-pong buffers back in their roles
+        after every replay; with the two-step pass an even number of PASSES is
+        recorded (``steps // 4 * 2``), closed by ``steps % 4`` single steps.
+        The graph holds steady-state steps only: ``capture`` first runs the
+        eager steps that needs (the first step sets up halo buffers, plan
+        cache and kernel variant; a fused step that primes the arena or
+        performs a pending entry barrier).
+        """
+        name = type(self).__name__
+        two = self._two_step_key()
+        if steps is None:
+            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
+        steps = int(steps)
+        if steps < 2 or steps % 2:
+            raise ValueError(f"{name}.capture: steps must be even and >= 2")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{name}.capture: hipGraphs need a GPU model")
+        self._capture_start()
+
+        def record():
+            singles = steps
+            if two is not None:
+                singles = steps % 4
+                for _ in range(steps // 4 * 2):
+                    self._pass()
+            for _ in range(singles):
+                self._step()  # no exit barrier inside the graph: run() drains once
+
+        self.graph = None
+        # fused steps exchange through their own peer mesh, not update_halo_
+        g = capture_graph(record, f"{name}.capture", uses_halo=not self.fused)
+        self.graph = g
+        self.graph_steps = steps
+        self._graph_two = two
+        self._graph_cfg = self._capture_cfg()
+
+    def run(self, nt: int) -> None:
+        """Advance ``nt`` steps (by graph replays of ``graph_steps`` steps if
+        captured); in fused mode one exit barrier at the end (``_drain``),
+        none between the steps.
+
+        A graph is replayed only if it was captured with the current settings
+        (pass key, ``_capture_cfg``). Its steps have their buffer roles baked
+        in and hold no entry barrier, so eager steps realign first: at most
+        two. For Acoustic2D the first clears a pending entry barrier and of any
+        two consecutive steps one starts from the captured buffer, so it is
+        ready within two. For a fused Diffusion3D the buffer and the step
+        counter's parity both alternate, and a mode switch between captures can
+        make the two disagree for good: then the rest runs eagerly."""
+        ran = nt > 0
+        two = self._two_step_key()
+        if self.graph is not None and self._graph_two == two and self._graph_cfg == self._capture_cfg():
+            for _ in range(2):
+                if nt == 0 or self._graph_ready():
+                    break
+                self._step()
+                nt -= 1
+            if self._graph_ready():
+                k = self.graph_steps
+                for _ in range(nt // k):
+                    self.graph.replay()
+                self._replayed(k * (nt // k))
+                nt %= k
+        if two is not None:
+            for _ in range(nt // 2):
+                self._pass()
+            nt %= 2
+        for _ in range(nt):
+            self._step()
+        if ran:
+            self._drain()
+
+    def save(self, prefix: str, step: int = 0) -> str:
+        """Per-rank checkpoint of the model state (collective; utils.checkpoint).
+        Materialises fused-mode halos first (``sync_halo``), so the files hold
+        consistent fields. The other ping-pong buffers are saved as they are:
+        the state of one step ago, or of two steps ago if a two-step pass ran
+        last (the next step rewrites them)."""
+        from ..utils.checkpoint import save_checkpoint
+
+        self.sync_halo()
+        return save_checkpoint(prefix, step=step, **{name: getattr(self, name) for name in self._fields})
+
+    def restore(self, prefix: str) -> int:
+        """Load a checkpoint written by ``save`` on the same decomposition into
+        the model's buffers (in place: captured graphs stay valid); returns the
+        saved step."""
+        from ..utils.checkpoint import load_checkpoint
+
+        meta, f = load_checkpoint(prefix, device=self.device)
+        for name in self._fields:
+            dst = getattr(self, name)
+            if f[name].shape != dst.shape or f[name].dtype != dst.dtype:
+                raise ValueError(f"{type(self).__name__}.restore: {name} is {tuple(f[name].shape)}/{f[name].dtype}, "
+                                 f"the model has {tuple(dst.shape)}/{dst.dtype}")
+            dst.copy_(f[name])
+        self.mark_modified()  # the fields' own halo planes hold these halos; neighbours store behind a barrier
+        return int(meta["step"])
+
+
+def grid_sides(ndims: int) -> list:
+    """``[left, right]`` per dimension: whether the grid's neighbour table has
+    an entry there as it is now (another rank, a periodic self-exchange, the
+    loopback emulation, which writes its sides into the table)."""
+    gg = _grid.global_grid()
+    return [[int(gg.neighbors[s, d]) != -1 for s in range(2)] for d in range(ndims)]
+
+
+def exchanging_dims(ndims: int) -> list:
+    """Dimensions in which update_halo_ moves anything on the grid as it is
+    now: a neighbour on either side."""
+    return [d for d, sd in enumerate(grid_sides(ndims)) if any(sd)]
+
+
+def peer_mesh(ndims: int) -> tuple:
+    """``(mesh, neighbours)`` for a native fused exchange: a dedicated
+    ``PeerMesh`` (collective over the grid) and the ``[left, right]`` neighbour
+    ranks per dimension."""
+    gg = _grid.global_grid()
+    nb = [[int(gg.neighbors[s, d]) for s in range(2)] for d in range(ndims)]
+    if gg.nprocs > 1:
+        return native.PeerMesh(gg.comm.rank, gg.comm.size, gg.comm._allgather_bytes), nb
+    # periodic / loopback single process: every neighbour is this rank
+    return native.PeerMesh(0, 1, lambda b: [bytes(b)]), [[0 if v >= 0 else -1 for v in row] for row in nb]
+
+
+def two_step_env(var: str) -> str:
+    """The two-step selection's mode from environment variable ``var``:
+    ``auto`` (default), ``0`` or ``1``."""
+    env = os.environ.get(var, "auto").strip().lower()
+    if env not in ("auto", "0", "1"):
+        raise ValueError(f"{var} must be auto, 0 or 1, got {env!r}")
+    return env
+
+
+def faster_pass(m, single: float, t: dict, label):
+    """Outcome of a two-step A/B: records the ms per step in
+    ``m.two_step_times`` (``single`` and ``label(candidate)``) and returns the
+    fastest pass candidate if its time PER STEP is below the single-step
+    kernel's, else None."""
+    m.two_step_times = {"single": round(single, 5)}
+    m.two_step_times.update({label(c): round(x, 5) for c, x in t.items()})
+    best = min(t, key=t.get)
+    return best if t[best] < single else None

@@ -38,10 +38,11 @@ from .. import parallel  # noqa: F401
 from .._native import native
 from ..ops import stencil as _stencil
 from ..parallel import grid as _grid
-from ..parallel.halo import capture_graph, update_halo_
+from ..parallel.halo import update_halo_
 from ..utils import placement as _placement
-from .diffusion3d import GRAPH_STEPS, TWOSTEP_GRAPH_STEPS
+from ..utils.fields import carve, ipc_limit
 from ..utils.tools import coords_g, nx_g, ny_g
+from ._pingpong import PingPongModel, exchanging_dims, faster_pass, peer_mesh, two_step_env
 
 # Chunk sizes (rows of x written per wave) the selection times the two-step
 # pass with. A chunk re-reads two rows of lead-in (2/chunk more input), a
@@ -51,7 +52,7 @@ from ..utils.tools import coords_g, nx_g, ny_g
 TWOSTEP_CHUNKS = (4, 8, 12, 16, 32)
 
 
-class Acoustic2D:
+class Acoustic2D(PingPongModel):
     """2-D staggered acoustic wave propagation (pressure P at cell centres,
     velocities Vx/Vy on staggered faces: nx+1 / ny+1) with one fused HIP kernel
     per step and one ``update_halo_(Vx2, Vy2)`` (mixed overlaps); the 2-D
@@ -71,8 +72,11 @@ class Acoustic2D:
     step ago after a single step and of TWO steps ago after a two-step pass
     (whatever runs next rewrites them either way)."""
 
+    _fields = ("P", "Vx", "Vy", "P2", "Vx2", "Vy2")
+
     def __init__(self, *, dtype=torch.float32, device=None, K: float = 1.0, rho: float = 1.0,
                  lx: float = 10.0, ly: float = 10.0):
+        super().__init__()
         gg = _grid.global_grid()
         nx, ny = int(gg.nxyz[0]), int(gg.nxyz[1])
         if int(gg.nxyz[2]) != 1:
@@ -94,10 +98,8 @@ class Acoustic2D:
         Vx = torch.zeros((nx + 1, ny), dtype=dtype, device=self.device)
         Vy = torch.zeros((nx, ny + 1), dtype=dtype, device=self.device)
         fields = [P, Vx, Vy, P.clone(), Vx.clone(), Vy.clone()]
-        import os as _os
-
         self.placement = None
-        if self.device.type == "cuda" and _os.environ.get("IGG_FIELD_MEMORY", "fine") != "torch":
+        if self.device.type == "cuda" and os.environ.get("IGG_FIELD_MEMORY", "fine") != "torch":
             # One fine-grained allocation (the fused exchange stores into the
             # neighbours' Vx2/Vy2 while their kernels run: docs/COHERENCE.md),
             # the fastest of several candidates (utils/placement.py: 0.282 vs
@@ -105,7 +107,10 @@ class Acoustic2D:
             init = fields
             nbytes = P.numel() * P.element_size()
             k = _placement.candidate_count(gg, nbytes, sum(t.numel() * t.element_size() for t in init), self.device)
-            fields, self.placement = _placement.placed(lambda: _carve_fine(init, split=int(gg.nprocs) > 1), k,
+            # (with neighbours in other processes, which map the velocity
+            # buffers, no allocation may reach the IPC size limit)
+            split_at = ipc_limit() if int(gg.nprocs) > 1 else None
+            fields, self.placement = _placement.placed(lambda: carve(init, kind=1, split_at=split_at), k,
                                                        self._time_placements)
             if self.placement is not None:  # the probe stepped the chosen carve: back to the initial state
                 for dst, src in zip(fields, init):
@@ -118,10 +123,7 @@ class Acoustic2D:
         # fused exchange relies on it: set_fused). P itself is never exchanged
         # again: P2 is recomputed everywhere from halo-consistent inputs.
         update_halo_(self.P)
-        self.graph = None
-        self.graph_steps = 2
         self._graph_P = 0  # P's buffer when the graph was captured
-        self._warm = False
         self.fused = False
         self._fa = None  # native FusedAcoustic (set_fused)
         # The next fused step starts with an entry barrier: the neighbours'
@@ -129,12 +131,10 @@ class Acoustic2D:
         # (switch into fused mode, restore, external edits: mark_modified).
         self._entry = True
         # Two-step pass: whether the selection kept it, its chunk (0: the
-        # kernel's default), the A/B's ms per step ("single", "c<chunk>") and
-        # the pass setting the graph was captured with (None: single steps).
+        # kernel's default) and the A/B's ms per step ("single", "c<chunk>").
         self.two_step = False
         self.two_step_chunk = 0
         self.two_step_times = {}
-        self._graph_two = None
         _select_two_step(self)
 
     def _two_step_now(self) -> bool:
@@ -143,10 +143,15 @@ class Acoustic2D:
         and the kernel takes the shape."""
         if not self.two_step or self.device.type != "cuda" or self.fused:
             return False
-        return _no_neighbours() and _stencil.acoustic2d_twostep_ok(self.P)
+        return not exchanging_dims(2) and _stencil.acoustic2d_twostep_ok(self.P)
 
-    def _two_step_key(self):
-        return int(self.two_step_chunk) if self._two_step_now() else None
+    def _pass_key(self):
+        return int(self.two_step_chunk)
+
+    def _swap(self) -> None:
+        self.P, self.P2 = self.P2, self.P
+        self.Vx, self.Vx2 = self.Vx2, self.Vx
+        self.Vy, self.Vy2 = self.Vy2, self.Vy
 
     def _pass(self) -> None:
         """Two time steps in one pass (callers checked ``_two_step_now``: no
@@ -156,9 +161,7 @@ class Acoustic2D:
                                   self.Vx.data_ptr(), self.Vy.data_ptr(), self.nx, self.ny, self.dt * self.K,
                                   self.dt / self.rho, 1.0 / self.dx, 1.0 / self.dy, self.P.element_size(),
                                   int(self.two_step_chunk), s)
-        self.P, self.P2 = self.P2, self.P
-        self.Vx, self.Vx2 = self.Vx2, self.Vx
-        self.Vy, self.Vy2 = self.Vy2, self.Vy
+        self._swap()
         self._warm = True
 
     def _time_placements(self, cands) -> list:
@@ -183,9 +186,7 @@ class Acoustic2D:
         """Fused exchange possible: GPU, a neighbour in x or y, overlap 2 in
         both, the vector kernel's shape (ny % 16 B-vector width, >= 5x5)."""
         gg = _grid.global_grid()
-        if self.device.type != "cuda":
-            return False
-        if not any(int(gg.neighbors[s, d]) != -1 for s in range(2) for d in range(2)):
+        if self.device.type != "cuda" or not exchanging_dims(2):
             return False
         if int(gg.overlaps[0]) != 2 or int(gg.overlaps[1]) != 2:
             return False
@@ -201,13 +202,7 @@ class Acoustic2D:
         if flag == self.fused:
             return flag
         if flag and self._fa is None:
-            gg = _grid.global_grid()
-            nb = [[int(gg.neighbors[s, d]) for s in range(2)] for d in range(2)]
-            if gg.nprocs > 1:
-                mesh = native.PeerMesh(gg.comm.rank, gg.comm.size, gg.comm._allgather_bytes)
-            else:  # periodic / loopback single process: every neighbour is this rank
-                nb = [[0 if v >= 0 else -1 for v in row] for row in nb]
-                mesh = native.PeerMesh(0, 1, lambda b: [bytes(b)])
+            mesh, nb = peer_mesh(2)
             self._fa = native.FusedAcoustic(mesh, self.nx, self.ny, self.P.element_size(), nb)
             self._fa.set_fields(self.Vx.data_ptr(), self.Vx2.data_ptr(), self.Vy.data_ptr(), self.Vy2.data_ptr())
         self.fused = flag
@@ -226,16 +221,9 @@ class Acoustic2D:
         """No-op: the fused step leaves every halo value as update_halo_ would
         (the API matches Diffusion3D's, whose fused step defers halo planes)."""
 
-    def clear_error(self) -> None:
-        """Reset the fused exchange's sticky timeout word on this rank (after
-        a failed fused step was handled, e.g. the fused exchange was dropped)."""
-        if self._fa is not None:
-            self._fa.clear_error()
-
-    def check(self) -> None:
-        """Raise if a fused-exchange sync kernel timed out waiting for a neighbour."""
-        if self._fa is not None:
-            self._fa.check_error()
+    @property
+    def _fused_handle(self):
+        return self._fa
 
     def close(self) -> None:
         """Release the fused exchange's peer mappings (collective: every rank)."""
@@ -245,21 +233,6 @@ class Acoustic2D:
             self._fa = None
             self.fused = False
             self.graph = None
-
-    def step(self) -> None:
-        """Advance one time step. In fused mode the fields are final when the
-        call returns (as far as stream order goes): the neighbours' stores of
-        this step into them precede later work on the stream (``_drain``)."""
-        self._step()
-        self._drain()
-
-    def _drain(self) -> None:
-        """Exit barrier of in-kernel synchronised fused steps (collective): the
-        last step's neighbour stores into this rank's fields are complete before
-        anything queued after it (a restore, a comparison, gather_, a mode
-        switch) touches the fields. No-op after a sync-kernel step."""
-        if self.fused:
-            self._fa.drain(torch.cuda.current_stream().cuda_stream)
 
     def _step(self) -> None:
         if self.fused:
@@ -272,9 +245,7 @@ class Acoustic2D:
         else:
             self._update(self.P2, self.Vx2, self.Vy2, self.P, self.Vx, self.Vy)
             update_halo_(self.Vx2, self.Vy2)
-        self.P, self.P2 = self.P2, self.P
-        self.Vx, self.Vx2 = self.Vx2, self.Vx
-        self.Vy, self.Vy2 = self.Vy2, self.Vy
+        self._swap()
         self._warm = True
 
     def local_step(self) -> None:
@@ -288,93 +259,18 @@ class Acoustic2D:
         drifts apart under local steps, and the fused step is bitwise equal to
         the update_halo_ path only from states where those copies agree."""
         self._update(self.P2, self.Vx2, self.Vy2, self.P, self.Vx, self.Vy)
-        self.P, self.P2 = self.P2, self.P
-        self.Vx, self.Vx2 = self.Vx2, self.Vx
-        self.Vy, self.Vy2 = self.Vy2, self.Vy
+        self._swap()
 
-    def capture(self, steps: int = None) -> None:
-        """hipGraph of ``steps`` (even; default GRAPH_STEPS, TWOSTEP_GRAPH_STEPS
-        while the two-step pass is on) time steps: buffers are back in their
-        roles after a replay; replay launch overhead (~9 us on MI355X) is paid
-        once per ``steps``. With the two-step pass an even number of PASSES is
-        recorded (``steps // 4 * 2``), closed by ``steps % 4`` single steps."""
-        if self.device.type != "cuda":
-            raise RuntimeError("Acoustic2D.capture: hipGraphs need a GPU model")
-        two = self._two_step_key()
-        if steps is None:
-            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
-        steps = int(steps)
-        if steps < 2 or steps % 2:
-            raise ValueError("Acoustic2D.capture: steps must be even and >= 2")
+    def _capture_start(self) -> None:
         if not self._warm or (self.fused and self._entry):
             self.step()  # the graph holds steady-state steps only (no entry barrier)
-        def record():
-            singles = steps
-            if two is not None:
-                singles = steps % 4
-                for _ in range(steps // 4 * 2):
-                    self._pass()
-            for _ in range(singles):
-                self._step()  # no exit barrier inside the graph: run() drains once
-
-        self.graph = None
-        # fused steps exchange through their own peer mesh, not update_halo_
-        g = capture_graph(record, f"{type(self).__name__}.capture", uses_halo=not self.fused)
-        self.graph = g
-        self.graph_steps = steps
         self._graph_P = self.P.data_ptr()
-        self._graph_two = two
-
-    def run(self, nt: int) -> None:
-        """Advance ``nt`` steps (graph replays where captured); one exit barrier
-        at the end in fused mode (``_drain``), none between the steps."""
-        ran = nt > 0
-        two = self._two_step_key()
-        if self.graph is not None and self._graph_two == two:
-            # The captured steps read the capture's P/Vx/Vy first and hold no
-            # entry barrier: one eager step realigns an odd step count or
-            # performs a pending barrier (mark_modified, restore).
-            while nt > 0 and not self._graph_ready():
-                self._step()
-                nt -= 1
-            for _ in range(nt // self.graph_steps):
-                self.graph.replay()
-            nt %= self.graph_steps
-        if two is not None:
-            for _ in range(nt // 2):
-                self._pass()
-            nt %= 2
-        for _ in range(nt):
-            self._step()
-        if ran:
-            self._drain()
 
     def _graph_ready(self) -> bool:
+        """The captured steps read the capture's P/Vx/Vy first and hold no
+        entry barrier (``run`` realigns an odd step count and performs a
+        pending barrier - mark_modified, restore - with eager steps)."""
         return self.P.data_ptr() == self._graph_P and not (self.fused and self._entry)
-
-    def save(self, prefix: str, step: int = 0) -> str:
-        """Per-rank checkpoint of the model state (collective; utils.checkpoint).
-        P2/Vx2/Vy2 are saved as they are: the state of one step ago, or of two
-        steps ago if a two-step pass ran last (the next step rewrites them)."""
-        from ..utils.checkpoint import save_checkpoint
-
-        return save_checkpoint(prefix, step=step, P=self.P, Vx=self.Vx, Vy=self.Vy, P2=self.P2, Vx2=self.Vx2,
-                               Vy2=self.Vy2)
-
-    def restore(self, prefix: str) -> int:
-        """Load a checkpoint written by ``save`` on the same decomposition (in
-        place); returns the saved step."""
-        from ..utils.checkpoint import load_checkpoint
-
-        meta, f = load_checkpoint(prefix, device=self.device)
-        for name in ("P", "Vx", "Vy", "P2", "Vx2", "Vy2"):
-            dst = getattr(self, name)
-            if f[name].shape != dst.shape or f[name].dtype != dst.dtype:
-                raise ValueError(f"Acoustic2D.restore: {name} is {tuple(f[name].shape)}/{f[name].dtype}, "
-                                 f"the model has {tuple(dst.shape)}/{dst.dtype}")
-            dst.copy_(f[name])
-        self._entry = True
-        return int(meta["step"])
 
     @property
     def a_eff_bytes(self) -> int:
@@ -384,13 +280,6 @@ class Acoustic2D:
         return 2 * (self.P.numel() + self.Vx.numel() + self.Vy.numel()) * self.P.element_size()
 
 
-def _no_neighbours() -> bool:
-    """No entry of the grid's neighbour table in x or y: no other rank, no
-    periodic self-exchange, no loopback emulation (update_halo_ is a no-op)."""
-    gg = _grid.global_grid()
-    return all(int(gg.neighbors[s, d]) == -1 for s in range(2) for d in range(2))
-
-
 def _select_two_step(m: "Acoustic2D") -> None:
     """Decide the two-step pass for this model (IGG_ACOUSTIC_TWOSTEP): 0 off,
     1 on where eligible (the kernel's default chunk), auto (default): the
@@ -398,11 +287,9 @@ def _select_two_step(m: "Acoustic2D") -> None:
     the model's own six buffers in the time loop's ping-pong shape,
     interleaved rounds, medians; the pass is kept only if its time PER STEP is
     lower. The fields are put back into their initial state afterwards."""
-    env = os.environ.get("IGG_ACOUSTIC_TWOSTEP", "auto").strip().lower()
-    if env not in ("auto", "0", "1"):
-        raise ValueError(f"IGG_ACOUSTIC_TWOSTEP must be auto, 0 or 1, got {env!r}")
+    env = two_step_env("IGG_ACOUSTIC_TWOSTEP")
     m.two_step, m.two_step_chunk, m.two_step_times = False, 0, {}
-    if env == "0" or m.device.type != "cuda" or not _no_neighbours() or not _stencil.acoustic2d_twostep_ok(m.P):
+    if env == "0" or m.device.type != "cuda" or exchanging_dims(2) or not _stencil.acoustic2d_twostep_ok(m.P):
         return
     if env == "1":
         m.two_step = True
@@ -424,35 +311,10 @@ def _select_two_step(m: "Acoustic2D") -> None:
             dst.copy_(src)
         torch.cuda.synchronize()
         del backup
-    m.two_step_times = {"single": round(single, 5)}
-    m.two_step_times.update({f"c{c}": round(x, 5) for c, x in t.items()})
-    best = min(t, key=t.get)
-    if t[best] < single:
+    best = faster_pass(m, single, t, lambda c: f"c{c}")
+    if best is not None:
         m.two_step_chunk = int(best)
         m.two_step = True
-
-
-def _carve_fine(tensors, split: bool = False):
-    """Copies of ``tensors`` carved from one native fine-grained allocation
-    (256 B-aligned slices). ``split``: if that allocation would reach the IPC
-    size limit (the neighbours map the velocity buffers), one allocation per
-    tensor instead."""
-    from .diffusion3d import _ipc_limit, native_buffer
-
-    sizes = [t.numel() * t.element_size() for t in tensors]
-    offs, pos = [], 0
-    for n in sizes:
-        offs.append(pos)
-        pos += -(-n // 256) * 256
-    if split and pos >= _ipc_limit() and len(tensors) > 1:
-        return [_carve_fine([t])[0] for t in tensors]
-    buf = native_buffer(pos, 1, tensors[0].device)
-    out = []
-    for t, o, n in zip(tensors, offs, sizes):
-        v = buf[o:o + n].view(t.dtype).view(t.shape)
-        v.copy_(t)
-        out.append(v)
-    return out
 
 
 def acoustic2d_reference(P, Vx, Vy, *, dt, K, rho, dx, dy):

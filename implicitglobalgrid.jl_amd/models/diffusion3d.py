@@ -38,17 +38,13 @@ import torch
 from .. import parallel  # noqa: F401
 from ..ops import stencil
 from ..parallel import grid as _grid
-from ..parallel.halo import capture_graph, update_halo_
+from ..parallel.halo import update_halo_
 from ..utils import placement as _placement
+from ..utils.fields import carve as _carve, ipc_limit, native_buffer  # noqa: F401
 from ..utils.tools import coords_g, nx_g, ny_g, nz_g
+from ._pingpong import (GRAPH_STEPS, TWOSTEP_GRAPH_STEPS, PingPongModel, exchanging_dims,  # noqa: F401
+                        faster_pass, grid_sides, peer_mesh, two_step_env)
 
-
-# Time steps per captured hipGraph (even): one replay launch (~9 us) per
-# GRAPH_STEPS steps instead of per 2 (profiles/r1_fused/graph_gaps.txt).
-GRAPH_STEPS = 10
-# While the two-step pass is on a graph holds passes, and an even number of
-# them hands the ping-pong buffers back in their roles: 20 steps = 10 passes.
-TWOSTEP_GRAPH_STEPS = 20
 # Candidates re-timed by the autotune's ping-pong stage (_choose_variant).
 PINGPONG_FRONT = 4
 # Whole-line z-edge stores of the full-box steps (ops.stencil.diffusion3d_
@@ -66,7 +62,7 @@ def _rccl_transport() -> bool:
     return H.transport_name() == "rccl"
 
 
-class Diffusion3D:
+class Diffusion3D(PingPongModel):
     """3-D heat diffusion with variable heat capacity on the local grid of the
     implicit global grid (examples/diffusion3D_multigpu_CuArrays_novis.jl):
     ``T2 = T + dt*lam/Cp * laplace(T)`` by one fused HIP kernel, then
@@ -92,10 +88,13 @@ class Diffusion3D:
     after a single step and of TWO steps ago after a two-step pass (it is
     rewritten by whatever runs next either way)."""
 
+    _fields = ("T", "T2", "Cp")
+
     def __init__(self, *, dtype=torch.float64, device=None, lam: float = 1.0, cp_min: float = 1.0,
                  lx: float = 10.0, ly: float = 10.0, lz: float = 10.0, overlap: bool = False,
                  slab_width=None, variant=None, halo_variant=None, interior_rounds: int = 0,
                  halo_rounds: int = 0, reserve_cus: int = 0, field_memory: str = None):
+        super().__init__()
         gg = _grid.global_grid()
         nx, ny, nz = (int(v) for v in gg.nxyz)
         if device is None:
@@ -126,9 +125,6 @@ class Diffusion3D:
         self.interior_rounds = interior_rounds
         self.halo_rounds = halo_rounds
         self.interior_first = False
-        self.graph = None
-        self.graph_steps = 2
-        self._warm = False
         shape = (nx, ny, nz)
         probe = torch.empty(shape, device="meta")  # sizes only, for coords_g
         kw = dict(dtype=torch.float64, device=self.device)
@@ -146,9 +142,7 @@ class Diffusion3D:
         # (profiles/r2_offsets/stencil_offsets.py: HBM channel placement). The
         # fields are allocated first and the initial conditions written into
         # them (no full-size temporary copies).
-        import os as _os
-
-        self.field_memory = (field_memory or _os.environ.get("IGG_FIELD_MEMORY", "fine")).strip().lower()
+        self.field_memory = (field_memory or os.environ.get("IGG_FIELD_MEMORY", "fine")).strip().lower()
         if self.field_memory not in ("torch", "fine", "vmm"):
             raise ValueError(f"Diffusion3D: field_memory must be 'torch', 'fine' or 'vmm', got {self.field_memory!r}")
         if self.device.type == "cuda":
@@ -162,11 +156,11 @@ class Diffusion3D:
             kinds = {"torch": None, "fine": 1, "vmm": 4}
             spec = [torch.empty(shape, dtype=dtype, device="meta")] * 3
             multi = int(gg.nprocs) > 1
-            big = multi and spec[0].numel() * spec[0].element_size() >= _ipc_limit()
+            big = multi and spec[0].numel() * spec[0].element_size() >= ipc_limit()
 
             def carve():
                 return _carve(spec, gap=266240, kind=kinds[self.field_memory],
-                              split_at=_ipc_limit() if multi else None, device=self.device,
+                              split_at=ipc_limit() if multi else None, device=self.device,
                               split_kind=4 if (big and self.field_memory == "fine") else None)
 
             (self.T, self.Cp, self.T2), self.placement = _placed_fields(carve, gg, spec[0], self.device)
@@ -188,7 +182,7 @@ class Diffusion3D:
                                                     - ((z - lz / 3.0) / 2) ** 2)
                                     + 50 * torch.exp(-((xs - lx / 2) / 2) ** 2 - ((y - ly / 2) / 2) ** 2
                                                      - ((z - lz / 1.5) / 2) ** 2))
-        if _wide_grid() and _exchanging():
+        if _wide_grid() and exchanging_dims(3):
             # On a periodic grid the analytic values of T and Cp in the halo
             # planes are not the images of the interior they overlap. A single
             # step reads only T's plane 0 of them and the exchange rewrites what
@@ -199,8 +193,7 @@ class Diffusion3D:
             # a non-periodic grid the values already agree).
             update_halo_(self.T, self.Cp)
         self.T2.copy_(self.T)
-        sides =[[bool(gg.neighbors[0, d] != -1), bool(gg.neighbors[1, d] != -1)] for d in range(3)]
-        self.sides = sides
+        self.sides = sides = grid_sides(3)
         # (the overlapped step's slabs and the fused exchange move one plane per side)
         self.can_overlap = self.device.type == "cuda" and any(any(sd) for sd in sides) and not _wide_grid()
         self.inner = [stencil.inner_box(shape)]
@@ -251,11 +244,8 @@ class Diffusion3D:
         # the primed halos live (arena, T's z halo column) and how the step
         # synchronises. A step in another form re-primes first (_align_form).
         self._fform = None
-        self._graph_fused = None  # fused mode / step parity the graph was captured with
-        self._graph_parity = 0
-        self._graph_cfg = None  # fused (variant, mode, rounds) of the capture
-        self._graph_T = 0  # T's buffer when the graph was captured
-        self._graph_two = None  # two-step (form, rounds) of the capture, None: single steps
+        self._graph_parity = 0  # step parity and T's buffer when the graph was captured
+        self._graph_T = 0
         _select_two_step(self)
 
     @property
@@ -290,8 +280,11 @@ class Diffusion3D:
             return False
         return _pass_halo_ok() and stencil.twostep_ok(self.T, self.two_step_form)
 
-    def _two_step_key(self):
-        return (self.two_step_form, self.two_step_rounds) if self._two_step_now() else None
+    def _pass_key(self):
+        return (self.two_step_form, self.two_step_rounds)
+
+    def _swap(self) -> None:
+        self.T, self.T2 = self.T2, self.T
 
     def _pass(self) -> None:
         """Two time steps in one pass (callers checked ``_two_step_now``), then
@@ -300,12 +293,12 @@ class Diffusion3D:
         planes keep T's values), which includes the send planes [2, 4) and
         [n-4, n-2); planes 0, 1, n-2, n-1 are what the exchange overwrites
         (next to a physical boundary plane 0 is fixed, so plane 1 is exact)."""
-        T, T2 = self.T, self.T2
-        stencil.diffusion3d_twostep_(T2, T, self.Cp, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy, dz=self.dz,
-                                     form=self.two_step_form, rounds=self.two_step_rounds, halo_z=HALO_Z)
-        if _exchanging():
-            update_halo_(T2)
-        self.T, self.T2 = T2, T
+        stencil.diffusion3d_twostep_(self.T2, self.T, self.Cp, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy,
+                                     dz=self.dz, form=self.two_step_form, rounds=self.two_step_rounds,
+                                     halo_z=HALO_Z)
+        if exchanging_dims(3):
+            update_halo_(self.T2)
+        self._swap()
         self._warm = True
 
     @property
@@ -335,7 +328,8 @@ class Diffusion3D:
             return flag
         if flag:
             if self._fh is None:
-                self._fh = _make_fused_halo(self)
+                mesh, nb = peer_mesh(3)
+                self._fh = stencil.native.FusedHalo(mesh, list(self.T.shape), self.T.element_size(), nb)
                 # Direct z sends (fused_mode bit 4) write into the neighbours'
                 # T/T2 while their kernels run: defined for fine-grained fields
                 # (docs/COHERENCE.md); torch-allocated fields only on one GPU.
@@ -389,42 +383,6 @@ class Diffusion3D:
             self._fh = None
             self.graph = None
 
-    def save(self, prefix: str, step: int = 0) -> str:
-        """Per-rank checkpoint of the model state (collective; utils.checkpoint).
-        Materialises fused-mode halos first, so the files hold consistent fields."""
-        from ..utils.checkpoint import save_checkpoint
-
-        self.sync_halo()
-        return save_checkpoint(prefix, step=step, T=self.T, T2=self.T2, Cp=self.Cp)
-
-    def restore(self, prefix: str) -> int:
-        """Load a checkpoint written by ``save`` on the same decomposition into
-        the model's buffers (in place: captured graphs stay valid); returns the
-        saved step."""
-        from ..utils.checkpoint import load_checkpoint
-
-        meta, f = load_checkpoint(prefix, device=self.device)
-        for name in ("T", "T2", "Cp"):
-            dst = getattr(self, name)
-            if f[name].shape != dst.shape or f[name].dtype != dst.dtype:
-                raise ValueError(f"Diffusion3D.restore: {name} is {tuple(f[name].shape)}/{f[name].dtype}, "
-                                 f"the model has {tuple(dst.shape)}/{dst.dtype}")
-            dst.copy_(f[name])
-        self._fprimed = False  # the fused arena does not hold these halos; T's own halo planes do
-        self._fentry = True
-        return int(meta["step"])
-
-    def clear_error(self) -> None:
-        """Reset the fused exchange's sticky timeout word on this rank (after
-        a failed fused step was handled, e.g. the fused exchange was dropped)."""
-        if self._fh is not None:
-            self._fh.clear_error()
-
-    def check(self) -> None:
-        """Raise if a fused-exchange sync kernel timed out waiting for a neighbour."""
-        if self._fh is not None:
-            self._fh.check_error()
-
     def set_overlap(self, flag: bool) -> bool:
         """Switch between the serial step and the boundary/interior overlapped
         step (needs a GPU model with at least one neighbour); returns the mode."""
@@ -455,20 +413,9 @@ class Diffusion3D:
                     variant=self.variant if variant is None else variant,
                     rounds=self.rounds if rounds is None else rounds)
 
-    def step(self) -> None:
-        """Advance one time step (T <- T2 after the update and halo exchange).
-        In fused mode the neighbours' stores of this step into this rank's
-        arena and fields precede later work on the stream (``_drain``)."""
-        self._step()
-        self._drain()
-
-    def _drain(self) -> None:
-        """Exit barrier of in-kernel synchronised fused steps (collective): the
-        last step's neighbour stores (arena, direct-z halo column) are complete
-        before anything queued after it touches them (sync_halo, a restore, a
-        comparison, gather_). No-op after a sync-kernel step."""
-        if self.fused:
-            self._fh.drain(torch.cuda.current_stream().cuda_stream)
+    @property
+    def _fused_handle(self):
+        return self._fh
 
     def _fused_step_mode(self) -> int:
         # direct z (bit 4) needs the registered field buffers; where they
@@ -566,7 +513,7 @@ class Diffusion3D:
             # update_halo_(T2) right after rewrites every exchanged one
             stencil.diffusion3d_(T2, T, Cp, boxes=self.inner, halo_z=self.halo_z, **self._kw())
             update_halo_(T2)
-        self.T, self.T2 = T2, T
+        self._swap()
         self._warm = True
 
     def local_step(self) -> None:
@@ -578,97 +525,32 @@ class Diffusion3D:
         Used by the bench's same-process efficiency E = t(local) / t(step).
         Leaves the halo planes unexchanged: timing only (callers that go on
         with real steps call ``exchange_halos`` afterwards)."""
-        T, T2 = self.T, self.T2
-        stencil.diffusion3d_(T2, T, self.Cp, boxes=self.inner, halo_z=self.halo_z, **self._kw())
-        self.T, self.T2 = T2, T
+        stencil.diffusion3d_(self.T2, self.T, self.Cp, boxes=self.inner, halo_z=self.halo_z, **self._kw())
+        self._swap()
 
-    def capture(self, steps: int = None) -> None:
-        """Record ``steps`` (even, default GRAPH_STEPS; TWOSTEP_GRAPH_STEPS
-        while the two-step pass is on) time steps in a hipGraph for ``run``.
-
-        A step is a chain of launches (stencil, pack, RCCL group, unpack per
-        dimension; or fused stencil + sync) whose gaps are host launch latency;
-        replaying a graph removes that latency, and a graph replay costs ~9 us
-        to launch on MI355X (profiles/r1_fused/), so several steps are captured
-        per graph. An even count puts the ping-pong buffers back in their roles
-        after every replay; with the two-step pass an even number of PASSES is
-        recorded, closed by two single steps when steps % 4 == 2. Needs one eager step first (halo buffers, plan
-        cache and kernel variant are set up outside the capture); ``capture``
-        performs that step itself if none ran yet (and one fused step if the
-        fused arena does not hold T's halos).
-        """
-        two = self._two_step_key()
-        if steps is None:
-            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
-        steps = int(steps)
-        if steps < 2 or steps % 2:
-            raise ValueError("Diffusion3D.capture: steps must be even and >= 2")
-        if self.device.type != "cuda":
-            raise RuntimeError("Diffusion3D.capture: hipGraphs need a GPU model")
+    def _capture_start(self) -> None:
         if not self._warm:
             self.step()
         if self.fused:
             self._align_form()  # no re-priming inside the capture
         if self.fused and not self._fprimed:
             self.step()  # captured fused steps read the arena: it must hold T's halos
-        def record():
-            singles = steps
-            if two is not None:
-                singles = steps % 4
-                for _ in range(steps // 4 * 2):
-                    self._pass()
-            for _ in range(singles):
-                self._step()  # no exit barrier inside the graph: run() drains once
-
-        self.graph = None
-        # fused steps exchange through their own peer mesh, not update_halo_
-        g = capture_graph(record, f"{type(self).__name__}.capture", uses_halo=not self.fused)
-        self.graph = g
-        self.graph_steps = steps
-        self._graph_fused = self.fused
-        self._graph_cfg = self._fused_cfg()
+        # The captured steps have their buffer roles baked in (T of the
+        # capture is read first) and, fused, their arena halves too: they
+        # assume a primed arena, no pending entry barrier and the step-counter
+        # parity of the capture (an even number of steps: as it is now).
         self._graph_parity = self._fstep % 2
         self._graph_T = self.T.data_ptr()
-        self._graph_two = two
 
-    def run(self, nt: int) -> None:
-        """Advance ``nt`` steps (by graph replays of ``graph_steps`` steps if
-        captured); in fused mode one exit barrier at the end (``_drain``)."""
-        ran = nt > 0
-        two = self._two_step_key()
-        if self.graph is not None and self._graph_fused == self.fused and self._graph_cfg == self._fused_cfg() \
-                and self._graph_two == two:
-            # The captured steps have their buffer roles baked in (T of the
-            # capture is read first) and, fused, their arena halves too: they
-            # assume a primed arena, no pending entry barrier and the
-            # step-counter parity of the capture. Eager steps realign (at most
-            # two; a mode switch between captures can make the two parities
-            # disagree for good: then the rest runs eagerly).
-            for _ in range(2):
-                if nt == 0 or self._graph_ready():
-                    break
-                self._step()
-                nt -= 1
-            if self._graph_ready():
-                k = self.graph_steps
-                for _ in range(nt // k):
-                    self.graph.replay()
-                if self.fused:
-                    self._fstep += k * (nt // k)
-                nt %= k
-        if two is not None:
-            for _ in range(nt // 2):
-                self._pass()
-            nt %= 2
-        for _ in range(nt):
-            self._step()
-        if ran:
-            self._drain()
-
-    def _fused_cfg(self):
-        """The fused kernel form a captured graph bakes in (a graph of another
-        form is not replayed: the steps run eagerly until the next capture)."""
+    def _capture_cfg(self):
+        """Fused mode and the fused kernel form a captured graph bakes in (a
+        graph of another form is not replayed: the steps run eagerly until the
+        next capture)."""
         return (self.fused_variant, self.fused_mode, self.fused_rounds) if self.fused else None
+
+    def _replayed(self, k: int) -> None:
+        if self.fused:
+            self._fstep += k
 
     def _graph_ready(self) -> bool:
         if self.T.data_ptr() != self._graph_T:
@@ -683,20 +565,12 @@ class Diffusion3D:
         return 3 * self.T.numel() * self.T.element_size()
 
 
-def _exchanging() -> list:
-    """Dimensions in which update_halo_ moves anything on the grid as it is
-    now: a neighbour on either side (another rank, a periodic self-exchange,
-    the loopback emulation, which writes its sides into the neighbour table)."""
-    gg = _grid.global_grid()
-    return [d for d in range(3) if any(int(gg.neighbors[s, d]) != -1 for s in range(2))]
-
-
 def _pass_halo_ok() -> bool:
     """The halo is deep enough for the two-step pass: at least two planes in
     every exchanging dimension (a dimension exchanges on every rank or on
     none, so all ranks agree)."""
     gg = _grid.global_grid()
-    return all(int(gg.halowidths[d]) >= 2 for d in _exchanging())
+    return all(int(gg.halowidths[d]) >= 2 for d in exchanging_dims(3))
 
 
 def _wide_grid() -> bool:
@@ -713,9 +587,7 @@ def _select_two_step(m: "Diffusion3D") -> None:
     steps; the times are summed over the ranks (every rank must make the same
     choice: one that exchanged every step would mismatch one that exchanges
     every two), and the timing itself is collective."""
-    env = os.environ.get("IGG_STENCIL_TWOSTEP", "auto").strip().lower()
-    if env not in ("auto", "0", "1"):
-        raise ValueError(f"IGG_STENCIL_TWOSTEP must be auto, 0 or 1, got {env!r}")
+    env = two_step_env("IGG_STENCIL_TWOSTEP")
     m.two_step = False
     if env == "0" or m.device.type != "cuda" or m.variant is None or not _pass_halo_ok():
         return
@@ -729,7 +601,7 @@ def _select_two_step(m: "Diffusion3D") -> None:
     rd2 = [1.0 / m.dx ** 2, 1.0 / m.dy ** 2, 1.0 / m.dz ** 2]
     boxes = [(list(b[0]), list(b[1])) for b in m.inner]
     cands = [(f, r, HALO_Z) for f in forms for r in stencil.GRID_ROUNDS]
-    exchanging = bool(_exchanging())
+    exchanging = bool(exchanging_dims(3))
     single, t = stencil.time_twostep_pingpong(m.T2, m.T, m.Cp, rd2, m.dt * m.lam, boxes,
                                               (int(m.variant), int(m.rounds), bool(m.halo_z)), cands,
                                               exchange=update_halo_ if exchanging else None)
@@ -741,10 +613,8 @@ def _select_two_step(m: "Diffusion3D") -> None:
         dist.all_reduce(tot, group=gg.comm.gloo)
         tot /= int(gg.nprocs)
         single, t = float(tot[0]), {c: float(x) for c, x in zip(cands, tot[1:])}
-    m.two_step_times = {"single": round(single, 5)}
-    m.two_step_times.update({f"t{f}@r{r}": round(x, 5) for (f, r, _hz), x in t.items()})
-    best = min(t, key=t.get)
-    if t[best] < single:
+    best = faster_pass(m, single, t, lambda c: f"t{c[0]}@r{c[1]}")
+    if best is not None:
         m.two_step_form, m.two_step_rounds = int(best[0]), int(best[1])
         m.two_step = True
 
@@ -767,54 +637,6 @@ def _serial_overlap(streams: int) -> bool:
     streams at GPU_MAX_HW_QUEUES=1; the full cell table is in its NOTES)."""
     q = _hw_queues()
     return q is not None and q < streams
-
-
-def _make_fused_halo(m: "Diffusion3D"):
-    """Native FusedHalo over a dedicated peer mesh (collective over the grid)."""
-    from .._native import native
-
-    gg = _grid.global_grid()
-    nb = [[int(gg.neighbors[s, d]) for s in range(2)] for d in range(3)]
-    if gg.nprocs > 1:
-        mesh = native.PeerMesh(gg.comm.rank, gg.comm.size, gg.comm._allgather_bytes)
-    else:  # periodic / loopback single process: every neighbour is this rank
-        nb = [[0 if v >= 0 else -1 for v in row] for row in nb]
-        mesh = native.PeerMesh(0, 1, lambda b: [bytes(b)])
-    return native.FusedHalo(mesh, list(m.T.shape), m.T.element_size(), nb)
-
-
-def _ipc_limit() -> int:
-    """Allocation size from which IPC export is refused (csrc/include/igg/ipc.hpp)."""
-    from .._native import native
-
-    return int(native.IPC_MAX_BYTES)
-
-
-def _carve(tensors, gap: int, kind=None, split_at=None, device=None, split_kind=None):
-    """Copies of equally sized tensors placed in one buffer ``gap`` bytes apart.
-    ``kind``: None = torch's caching allocator, else a native MemKind (1 =
-    fine-grained, 4 = HIP VMM) allocated by the runtime and handed over through
-    DLPack. ``split_at``: if the one buffer would reach this many bytes, one
-    allocation per tensor instead (the IPC size limit), of MemKind
-    ``split_kind`` if given. Meta tensors give shape and dtype only:
-    uninitialised views on ``device``."""
-    nbytes = tensors[0].numel() * tensors[0].element_size()
-    stride = nbytes + gap
-    device = tensors[0].device if device is None else device
-    if split_at is not None and stride * len(tensors) >= split_at and len(tensors) > 1:
-        k = kind if split_kind is None else split_kind
-        return [_carve([t], 0, k, device=device)[0] for t in tensors]
-    if kind is None:
-        buf = torch.empty(stride * len(tensors), dtype=torch.uint8, device=device)
-    else:
-        buf = native_buffer(stride * len(tensors), kind, device)
-    out = []
-    for k, t in enumerate(tensors):
-        v = buf[k * stride:k * stride + nbytes].view(t.dtype).view(t.shape)
-        if t.device.type != "meta":
-            v.copy_(t)
-        out.append(v)
-    return out
 
 
 def _placed_fields(carve, gg, meta: torch.Tensor, device):
@@ -852,23 +674,10 @@ def _time_placements(cands, dtype, v=None, rounds: int = 3, halo_z: bool = False
     return _placement.time_candidates(cands, launch, steps=steps)
 
 
-def native_buffer(nbytes: int, kind: int, device) -> torch.Tensor:
-    """1-D uint8 device tensor of ``nbytes`` in native memory of MemKind
-    ``kind`` (csrc/include/igg/ipc.hpp), owned by torch (freed with it)."""
-    from torch.utils import dlpack
-
-    from .._native import native
-
-    with torch.cuda.device(device):
-        return dlpack.from_dlpack(native.alloc_dlpack(int(nbytes), int(kind)))
-
-
 def _choose_variant(m: "Diffusion3D") -> int:
     """Kernel variant for this model: IGG_STENCIL_VARIANT if it is an integer,
     else the fastest of the shortlist timed on the model's own arrays, summed
     over all ranks so every rank runs the same kernel."""
-    import os
-
     env = os.environ.get("IGG_STENCIL_VARIANT", "auto").strip().lower()
     if env != "auto":
         return int(env)

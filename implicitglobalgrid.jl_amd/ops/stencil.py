@@ -12,11 +12,13 @@ CPU tensors run the threaded C++ host kernel.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
 
 from .._native import IGGError, native
+from ..utils.timing import interleaved_medians
 
 _autotune_cache: dict = {}
 
@@ -92,6 +94,30 @@ def _cand(c, halo_z: bool):
     return (int(c[0]), int(c[1]), bool(c[2]) if len(c) > 2 else halo_z)
 
 
+def _single_step_launcher(T, Cp, rd2, dtlam, boxes):
+    """``launch((variant, grid rounds, halo_z), dst, src)``: one single-step
+    kernel between buffers shaped like ``T`` on the current stream."""
+    n, es, s = list(T.shape), T.element_size(), torch.cuda.current_stream().cuda_stream
+
+    def launch(cand, dst, src):
+        v, gr, hz = cand
+        native.diffusion3d(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, boxes, True, v, s, gr, hz)
+
+    return launch
+
+
+@contextlib.contextmanager
+def _kept(T):
+    """Save ``T`` and put it back on the way out, also when a launch raises."""
+    backup = T.clone()
+    try:
+        yield
+    finally:
+        T.copy_(backup)
+        torch.cuda.synchronize()
+        del backup
+
+
 def time_variants(T2, T, Cp, rd2, dtlam, boxes, candidates=None, reps: int = 5, rounds: int = 3,
                   halo_z: bool = False) -> dict:
     """Median-of-rounds time (ms) of each candidate on these arrays, interleaved
@@ -99,28 +125,14 @@ def time_variants(T2, T, Cp, rd2, dtlam, boxes, candidates=None, reps: int = 5, 
     a variant index, a (variant, grid_rounds) pair (grid residency rounds of
     the launch, see diffusion3d_) or a (variant, grid_rounds, halo_z) triple
     (``halo_z`` applies to the others)."""
-    n = list(T.shape)
     cands = compiled_variants() if candidates is None else list(candidates)
-    s = torch.cuda.current_stream()
-    times = {c: [] for c in cands}
+    launch = _single_step_launcher(T, Cp, rd2, dtlam, boxes)
 
-    def launch(c):
-        v, gr, hz = _cand(c, halo_z)
-        native.diffusion3d(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, T.element_size(), boxes, True,
-                           v, s.cuda_stream, gr, hz)
+    def run(c, k):
+        for _ in range(k):
+            launch(_cand(c, halo_z), T2, T)
 
-    for v in cands:  # warm every code object once
-        launch(v)
-    for _ in range(rounds):
-        for v in cands:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            for _ in range(reps):
-                launch(v)
-            e1.record(s)
-            e1.synchronize()
-            times[v].append(e0.elapsed_time(e1) / reps)
-    return {v: sorted(t)[len(t) // 2] for v, t in times.items()}
+    return dict(zip(cands, interleaved_medians(cands, run, reps, rounds, warm=1)))  # warm: every code object once
 
 
 def time_variants_pingpong(T2, T, Cp, rd2, dtlam, boxes, candidates, steps: int = 10, rounds: int = 3,
@@ -130,37 +142,15 @@ def time_variants_pingpong(T2, T, Cp, rd2, dtlam, boxes, candidates, steps: int 
     buffers (their HBM placement alternates exactly as in the run). T is saved
     and restored around the measurement; T2's interior is scribbled (it is
     overwritten by the next step anyway)."""
-    n = list(T.shape)
-    s = torch.cuda.current_stream()
-    times = {c: [] for c in candidates}
-    backup = T.clone()
+    cands = list(candidates)
+    launch = _single_step_launcher(T, Cp, rd2, dtlam, boxes)
 
-    def launch(c, dst, src):
-        v, gr, hz = _cand(c, halo_z)
-        native.diffusion3d(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, T.element_size(), boxes,
-                           True, v, s.cuda_stream, gr, hz)
+    def run(c, k):
+        for j in range(k):
+            launch(_cand(c, halo_z), *((T2, T) if j % 2 == 0 else (T, T2)))
 
-    try:
-        for c in candidates:
-            launch(c, T2, T)
-            launch(c, T, T2)
-        for _ in range(rounds):
-            for c in candidates:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(s)
-                for k in range(steps):
-                    if k % 2 == 0:
-                        launch(c, T2, T)
-                    else:
-                        launch(c, T, T2)
-                e1.record(s)
-                e1.synchronize()
-                times[c].append(e0.elapsed_time(e1) / steps)
-    finally:
-        T.copy_(backup)
-        torch.cuda.synchronize()
-        del backup
-    return {c: sorted(t)[len(t) // 2] for c, t in times.items()}
+    with _kept(T):
+        return dict(zip(cands, interleaved_medians(cands, run, steps, rounds, warm=2)))
 
 
 def autotune(T2, T, Cp, rd2, dtlam, boxes, reps: int = 5, candidates=None) -> int:
@@ -243,47 +233,24 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
     follows every kernel on the buffer just written, as in the time loop: one
     exchange per step against one per pass (collective: every rank runs the
     same candidates in the same order). Returns (single ms, {candidate: ms})."""
-    n = list(T.shape)
-    s = torch.cuda.current_stream()
-    es = T.element_size()
-    backup = T.clone()
+    n, es, s = list(T.shape), T.element_size(), torch.cuda.current_stream().cuda_stream
+    launch = _single_step_launcher(T, Cp, rd2, dtlam, boxes)
 
     def run(c, k):
-        if c is None:
-            v, gr, hz = single
-            for j in range(k):
-                dst, src = (T2, T) if j % 2 == 0 else (T, T2)
-                native.diffusion3d(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, boxes, True,
-                                   v, s.cuda_stream, gr, hz)
-                if exchange is not None:
-                    exchange(dst)
-        else:
-            f, gr, hz = c
-            for j in range(k // 2):
-                dst, src = (T2, T) if j % 2 == 0 else (T, T2)
-                native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f,
-                                           s.cuda_stream, gr, hz)
-                if exchange is not None:
-                    exchange(dst)
+        for j in range(k if c is None else k // 2):
+            dst, src = (T2, T) if j % 2 == 0 else (T, T2)
+            if c is None:
+                launch(single, dst, src)
+            else:
+                f, gr, hz = c
+                native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f, s, gr,
+                                           hz)
+            if exchange is not None:
+                exchange(dst)
 
-    order = [None] + list(candidates)
-    times = {c: [] for c in order}
-    try:
-        for c in order:
-            run(c, 4)
-        for _ in range(rounds):
-            for c in order:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(s)
-                run(c, steps)
-                e1.record(s)
-                e1.synchronize()
-                times[c].append(e0.elapsed_time(e1) / steps)
-    finally:
-        T.copy_(backup)
-        torch.cuda.synchronize()
-        del backup
-    med = {c: sorted(t)[len(t) // 2] for c, t in times.items()}
+    order = [None] + list(candidates)  # None: the single-step candidate
+    with _kept(T):
+        med = dict(zip(order, interleaved_medians(order, run, steps, rounds, warm=4)))
     return med.pop(None), med
 
 
@@ -347,30 +314,16 @@ def time_acoustic_twostep_pingpong(a, b, launch_single, launch_pass, chunks, ste
     a multiple of 4: an even number of passes). ``launch_single(dst, src)`` /
     ``launch_pass(dst, src, chunk)`` launch on the current stream. Both triples
     are scribbled (callers restore them). Returns (single ms, {chunk: ms})."""
-    s = torch.cuda.current_stream()
-
     def run(c, k):
-        n = k if c is None else k // 2
-        for j in range(n):
+        for j in range(k if c is None else k // 2):
             dst, src = (b, a) if j % 2 == 0 else (a, b)
             if c is None:
                 launch_single(dst, src)
             else:
                 launch_pass(dst, src, c)
 
-    order = [None] + list(chunks)
-    times = {c: [] for c in order}
-    for c in order:
-        run(c, 4)
-    for _ in range(rounds):
-        for c in order:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            run(c, steps)
-            e1.record(s)
-            e1.synchronize()
-            times[c].append(e0.elapsed_time(e1) / steps)
-    med = {c: sorted(t)[len(t) // 2] for c, t in times.items()}
+    order = [None] + list(chunks)  # None: the single-step kernel
+    med = dict(zip(order, interleaved_medians(order, run, steps, rounds, warm=4)))
     return med.pop(None), med
 
 

@@ -35,6 +35,8 @@ import os
 
 import torch
 
+from .timing import interleaved_medians
+
 CANDIDATES = 16
 MAX_CANDIDATES = 64
 SPREAD = 1.025  # fast and slow carves differ by 4.5-6 %; the noise of one probe is < 0.5 %
@@ -68,21 +70,11 @@ def time_candidates(cands, launch, steps: int = 6, rounds: int = 3, warm: int = 
     """Median ms per step of each candidate. ``launch(cand, j)`` enqueues
     ping-pong step ``j`` on the current stream. Rounds are interleaved over
     the candidates, so a drifting clock affects all of them alike."""
-    s = torch.cuda.current_stream()
-    for c in cands:
-        for j in range(warm):
+    def run(c, k):
+        for j in range(k):
             launch(c, j)
-    times = [[] for _ in cands]
-    for _ in range(rounds):
-        for i, c in enumerate(cands):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            for j in range(steps):
-                launch(c, j)
-            e1.record(s)
-            e1.synchronize()
-            times[i].append(e0.elapsed_time(e1) / steps)
-    return [sorted(t)[len(t) // 2] for t in times]
+
+    return interleaved_medians(cands, run, steps, rounds, warm)
 
 
 def placed(carve, count, timer):

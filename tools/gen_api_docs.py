@@ -30,6 +30,7 @@ SECTIONS = [
     ("Applications", "igg.models.diffusion3d", ["Diffusion3D"]),
     ("", "igg.models.acoustic2d", ["Acoustic2D"]),
     ("Field placement", "igg.utils.placement", ["candidate_count", "time_candidates", "placed"]),
+    ("Timing A/Bs", "igg.utils.timing", ["interleaved_medians"]),
     ("Tracing", "igg.utils.trace", None),
     ("Launcher", "igg.utils.launch", ["launch", "main"]),
 ]
