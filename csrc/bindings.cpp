@@ -19,6 +19,7 @@
 #include "igg/coherence.hpp"
 #include "igg/comm.hpp"
 #include "igg/copy.hpp"
+#include "igg/copy_plan.hpp"
 #include "igg/fault.hpp"
 #include "igg/fused.hpp"
 #include "igg/gather.hpp"
@@ -447,6 +448,43 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("system") = false,
         "Batched strided 3-extent copies (slab kernel): boxes are (n_outer, n_mid, n_inner, src strides, dst "
         "strides), strides in elements.");
+
+  m.def("copy2d_plan",
+        [](const std::tuple<uintptr_t, uintptr_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>& c,
+           int elem_bytes) {
+          const CopyPlan2 p = plan_copy2d(
+              {reinterpret_cast<const char*>(std::get<0>(c)), reinterpret_cast<char*>(std::get<1>(c)),
+               std::get<2>(c), std::get<3>(c), std::get<4>(c), std::get<5>(c), std::get<6>(c), std::get<7>(c)},
+              elem_bytes, g_copy_gather);
+          py::dict d;
+          d["box"] = py::make_tuple(p.box.n_outer, p.box.n_inner, p.box.src_so, p.box.src_si, p.box.dst_so,
+                                    p.box.dst_si);
+          d["path"] = copy_path_name(p.path);
+          d["vec_bytes"] = p.vec_bytes;
+          d["blocks"] = p.blocks;
+          return d;
+        },
+        py::arg("copy"), py::arg("elem_bytes"),
+        "What launch_copy2d does with one copy: box (n_outer, n_inner, src strides, dst strides), path "
+        "(flat / gather / chunk), vec_bytes (0) and blocks.");
+
+  m.def("copy3d_plan",
+        [](const std::array<int64_t, 9>& b, const std::pair<uintptr_t, uintptr_t>& ptrs, int elem_bytes) {
+          const CopyPlan3 p = plan_copy3d(
+              {reinterpret_cast<const char*>(ptrs.first), reinterpret_cast<char*>(ptrs.second), b[0], b[1], b[2],
+               b[3], b[4], b[5], b[6], b[7], b[8]},
+              elem_bytes, ParityShift{}, g_copy_gather);
+          py::dict d;
+          d["box"] = py::make_tuple(p.box.n_outer, p.box.n_mid, p.box.n_inner, p.box.src_so, p.box.src_sm,
+                                    p.box.src_si, p.box.dst_so, p.box.dst_sm, p.box.dst_si);
+          d["path"] = copy_path_name(p.path);
+          d["vec_bytes"] = p.vec_bytes;
+          d["blocks"] = p.blocks;
+          return d;
+        },
+        py::arg("box"), py::arg("ptrs"), py::arg("elem_bytes"),
+        "What launch_copy3d does with one box: the normalised box (extents, src strides, dst strides), path "
+        "(flat / gather / chunk), vec_bytes (0, 4, 8 or 16) and blocks.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

@@ -12,22 +12,22 @@
 #include <cstdlib>
 
 #include "igg/copy.hpp"
+#include "igg/copy_plan.hpp"
 #include "igg/devsync.hpp"
 #include "igg/sysstore.hpp"
 
 namespace igg {
 
-extern bool g_copy_gather;
-
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int EPT = 4;                         // elements per thread per chunk
-constexpr int64_t CHUNK = BLOCK * EPT;         // elements of a row per workgroup
+// (the values live in igg/copy_plan.hpp: the host-side plan counts blocks with them)
+constexpr int BLOCK = COPY_BLOCK;
+constexpr int EPT = COPY_EPT;                  // elements per thread per chunk
+constexpr int64_t CHUNK = COPY_CHUNK;          // elements of a row per workgroup
 // Strided rows (gather path): a wave covers 64 consecutive inner elements of
 // GROWS outer rows, so each lane keeps GROWS independent line loads in flight;
 // a workgroup is 4 such waves (4 * GROWS outer rows).
-constexpr int GROWS = 8;
+constexpr int GROWS = COPY_GROWS;
 
 // 16-B elements (complex128): a vector type, which stays in VGPRs; a struct
 // element of the GROWS-deep load array was kept in scratch (144 B per lane,
@@ -155,15 +155,13 @@ void launch_typed(const std::vector<Copy2D>& copies, hipStream_t stream, const P
       const Copy2D& c = copies[pos++];
       const int64_t total = c.n_outer * c.n_inner;
       if (total <= 0) continue;
-      const bool is_flat = c.n_inner < 64;
-      const bool is_gather = !is_flat && (c.src_si != 1 || c.dst_si != 1) && g_copy_gather;
-      batch.c[batch.n] = c;
+      const CopyPlan2 p = plan_copy2d(c, static_cast<int>(sizeof(T)), g_copy_gather);
+      if (p.blocks <= 0) continue;
+      batch.c[batch.n] = p.box;
       batch.block_start[batch.n] = blocks;
-      if (is_flat) batch.flat_mask |= 1u << batch.n;
-      if (is_gather) batch.gather_mask |= 1u << batch.n;
-      blocks += is_flat     ? (total + BLOCK - 1) / BLOCK
-                : is_gather ? ((c.n_inner + 63) / 64) * ((c.n_outer + 4 * GROWS - 1) / (4 * GROWS))
-                            : c.n_outer * ((c.n_inner + CHUNK - 1) / CHUNK);
+      if (p.path == CopyPath::flat) batch.flat_mask |= 1u << batch.n;
+      if (p.path == CopyPath::gather) batch.gather_mask |= 1u << batch.n;
+      blocks += p.blocks;
       ++batch.n;
     }
     if (batch.n == 0) continue;
@@ -327,49 +325,6 @@ __global__ void __launch_bounds__(BLOCK) copy3d_batch_kernel(const CopyBatch3 ba
   if (FENCE) __builtin_amdgcn_s_waitcnt(0);  // as in copy2d_batch_kernel
 }
 
-// Merge extents that are adjacent in memory on both sides, then order the box
-// for the kernel's shapes. The element order of the copy does not change.
-Copy3D normalized(Copy3D c) {
-  if (c.n_mid > 1 && c.src_sm == c.n_inner * c.src_si && c.dst_sm == c.n_inner * c.dst_si) {
-    c.n_inner *= c.n_mid;
-    c.n_mid = 1;
-  } else if (c.n_inner == 1 && c.n_mid > 1) {
-    c.n_inner = c.n_mid, c.src_si = c.src_sm, c.dst_si = c.dst_sm;
-    c.n_mid = 1;
-  }
-  if (c.n_mid == 1) {
-    c.n_mid = c.n_outer, c.src_sm = c.src_so, c.dst_sm = c.dst_so;
-    c.n_outer = 1;
-  }
-  // (short rows keep n_outer when there are enough of them for a wave: the
-  // one-row-per-lane shape takes its GROWS independent loads from it)
-  if (c.n_outer > 1 && c.src_so == c.n_mid * c.src_sm && c.dst_so == c.n_mid * c.dst_sm &&
-      (c.n_inner >= 64 || c.n_mid < 64)) {
-    c.n_mid *= c.n_outer;
-    c.n_outer = 1;
-  }
-  // now the box is n_outer x n_mid rows of n_inner, n_outer > 1 only with n_mid > 1
-  if (c.n_outer == 1 && c.n_inner >= 64 && (c.src_si != 1 || c.dst_si != 1)) {
-    // long strided rows (a one-plane z face in a batch with slabs): one
-    // element per lane along the row, GROWS rows per lane
-    c.n_outer = c.n_mid, c.src_so = c.src_sm, c.dst_so = c.dst_sm;
-    c.n_mid = c.n_inner, c.src_sm = c.src_si, c.dst_sm = c.dst_si;
-    c.n_inner = 1;
-  }
-  if (c.n_outer == 1) c.src_so = c.dst_so = 0;
-  return c;
-}
-
-bool aligned_rows(const Copy3D& c, int eb, const ParityShift& par) {
-  const int64_t rb = c.n_inner * eb;
-  if (c.src_si != 1 || c.dst_si != 1 || (rb != 4 && rb != 8 && rb != 16)) return false;
-  if (par.side != 0 && par.bytes % rb != 0) return false;
-  auto ok = [&](const char* p, int64_t sm, int64_t so) {
-    return reinterpret_cast<uintptr_t>(p) % rb == 0 && (sm * eb) % rb == 0 && (so * eb) % rb == 0;
-  };
-  return ok(c.src, c.src_sm, c.src_so) && ok(c.dst, c.dst_sm, c.dst_so);
-}
-
 template <typename T, bool FENCE>
 void launch_typed3(const std::vector<Copy3D>& copies, hipStream_t stream, const ParityShift& par,
                    const CopyWait& wait) {
@@ -387,17 +342,14 @@ void launch_typed3(const std::vector<Copy3D>& copies, hipStream_t stream, const 
       const Copy3D& in = copies[pos++];
       const int64_t total = in.n_outer * in.n_mid * in.n_inner;
       if (total <= 0) continue;
-      const Copy3D c = normalized(in);
-      const bool is_gather = c.n_inner < 64 && c.n_mid >= 64 && g_copy_gather;
-      const bool is_flat = !is_gather && c.n_inner < 64;
-      batch.c[batch.n] = c;
+      const CopyPlan3 p = plan_copy3d(in, static_cast<int>(sizeof(T)), par, g_copy_gather);
+      if (p.blocks <= 0) continue;
+      batch.c[batch.n] = p.box;
       batch.block_start[batch.n] = blocks;
-      if (is_flat) batch.flat_mask |= 1u << batch.n;
-      if (is_gather) batch.gather_mask |= 1u << batch.n;
-      if (is_gather && aligned_rows(c, static_cast<int>(sizeof(T)), par)) batch.vec_mask |= 1u << batch.n;
-      blocks += is_flat     ? (total + BLOCK - 1) / BLOCK
-                : is_gather ? ((c.n_mid + 63) / 64) * ((c.n_outer + 4 * GROWS - 1) / (4 * GROWS))
-                            : c.n_outer * c.n_mid * ((c.n_inner + CHUNK - 1) / CHUNK);
+      if (p.path == CopyPath::flat) batch.flat_mask |= 1u << batch.n;
+      if (p.path == CopyPath::gather) batch.gather_mask |= 1u << batch.n;
+      if (p.vec_bytes) batch.vec_mask |= 1u << batch.n;
+      blocks += p.blocks;
       ++batch.n;
     }
     if (batch.n == 0) continue;

@@ -8,7 +8,9 @@ import pytest
 import torch
 
 import igg
+from igg._native import native
 from igg.parallel import halo as H
+from tests.copy_oracle import field_slab
 from tests.test_wide_halo_cpu import run_wide_ranks
 
 pytestmark = pytest.mark.gpu
@@ -56,16 +58,18 @@ def _host_exchange(fields):
 # in a permuted layout (the slab dimension is not the unit stride). A periodic
 # grid needs n >= 2*overlap-1 = 11 with width 3, so the two small shapes grow
 # to the smallest admissible sizes there, keeping what they exercise.
+# Width 4 (overlap 8, so n >= 15): the z slab's row is one 16-byte access with
+# 4-byte elements, 8 bytes with 2-byte and 4 bytes with 1-byte elements.
 SHAPES = {
-    "flat": {1: (8, 8, 8), 2: (8, 8, 8), 3: (11, 11, 11)},
-    "wave": {1: (9, 10, 70), 2: (9, 10, 70), 3: (11, 12, 70)},
-    "odd": {1: (12, 67, 131), 2: (12, 67, 131), 3: (12, 67, 131)},
-    "permuted": {1: (12, 67, 131), 2: (12, 67, 131), 3: (12, 67, 131)},
+    "flat": {1: (8, 8, 8), 2: (8, 8, 8), 3: (11, 11, 11), 4: (15, 15, 15)},
+    "wave": {1: (9, 10, 70), 2: (9, 10, 70), 3: (11, 12, 70), 4: (15, 16, 72)},
+    "odd": {1: (12, 67, 131), 2: (12, 67, 131), 3: (12, 67, 131), 4: (16, 67, 131)},
+    "permuted": {1: (12, 67, 131), 2: (12, 67, 131), 3: (12, 67, 131), 4: (16, 67, 131)},
 }
 
 
 @pytest.mark.parametrize("case", list(SHAPES))
-@pytest.mark.parametrize("w", [1, 2, 3])
+@pytest.mark.parametrize("w", [1, 2, 3, 4])
 def test_slab_exchange_matches_host(gpu, w, case):
     n = SHAPES[case][w]
     igg.init_global_grid(*n, periodx=1, periody=1, periodz=1, **_wide(w), **KW)
@@ -76,6 +80,13 @@ def test_slab_exchange_matches_host(gpu, w, case):
             ref, = _host_exchange([A])
             Ag = A.to(gpu)
             assert Ag.stride() == A.stride()
+            if w == 4 and case == "wave":
+                # the z slab of this exchange takes the vector rows named above
+                mv = field_slab(n, 2, 4, 4)["move"]
+                p = Ag.data_ptr()
+                eb = Ag.element_size()
+                plan = native.copy3d_plan(list(mv["box"]), (p + mv["src_off"] * eb, p + mv["dst_off"] * eb), eb)
+                assert (plan["path"], plan["vec_bytes"]) == ("gather", 4 * eb if eb <= 4 else 0), (dtype, plan)
             igg.update_halo_(Ag)
             assert torch.equal(Ag.cpu(), ref), f"{dtype} layout {order}"
     # two staggered fields in one launch
@@ -135,6 +146,30 @@ def test_loopback_wide_exchange(gpu, monkeypatch, transport, mode):
                 assert torch.equal(g.cpu(), r), f"{transport} {mode} {dtype}"
     if mode == "onephase" or transport == "put":
         assert H.engine().last_message_count == 52  # 26 directions x 2 fields, as with width 1
+    H.check_transport()
+    igg.finalize_global_grid(finalize_MPI=False)
+
+
+@pytest.mark.parametrize("w", [1, 2, 4])
+def test_loopback_put_exchange_every_element_size(gpu, monkeypatch, w):
+    """The put transport's system-scope stores with every element size (width
+    1: the 2-D kernel; 2 and 4: the slab kernel, scalar and vector rows), into
+    both arena halves: the only route to the system stores combined with the
+    arena's parity shift."""
+    monkeypatch.setenv("IGG_TRANSPORT", "put")
+    igg.init_global_grid(*N_LB, periodx=1, periody=1, periodz=1, **_wide(w), **KW)
+    refs = {}
+    for dtype in DTYPES:
+        fields = [_data(N_LB, dtype), _data((N_LB[0] + 1, N_LB[1], N_LB[2]), dtype)]
+        refs[dtype] = (fields, _host_exchange(fields))  # before the loopback: the periodic host exchange
+    H.enable_loopback()
+    for dtype, (fields, want) in refs.items():
+        for half in range(2):
+            got = [f.to(gpu) for f in fields]
+            igg.update_halo_(*got)
+            torch.cuda.synchronize()
+            for g, r in zip(got, want):
+                assert torch.equal(g.cpu(), r), f"put width {w} {dtype} exchange {half}"
     H.check_transport()
     igg.finalize_global_grid(finalize_MPI=False)
 
