@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Run selected stencil variants a few times on n^3 (for rocprofv3 counters);
-``--twostep FORMS`` launches the two-step pass (ms per PASS = two steps)."""
+``--twostep FORMS`` launches the two-step pass (ms per PASS = two steps),
+``--quotient`` also with the quotient array Q = dtlam/Cp as its input."""
 import argparse
 import os
 import sys
@@ -20,6 +21,7 @@ ap.add_argument("--rounds", default="0", help="grid residency rounds per launch 
 ap.add_argument("--twostep", default="", help="two-step forms to launch (list, e.g. 0,1,2), after the variants")
 ap.add_argument("--no-variants", action="store_true", help="launch no single-step variant (profile the pass alone)")
 ap.add_argument("--halo-z", action="store_true", help="whole-line z-edge stores")
+ap.add_argument("--quotient", default="0", help="two-step pass input (list): 0 = Cp, 1 = the quotient array Q")
 ap.add_argument("--calib", action="store_true", help="also run T2.copy_(T) (known bytes) for counter calibration")
 ap.add_argument("--placement", action="store_true",
                 help="fields on the fastest of the placement probe's candidate carves (utils/placement.py)")
@@ -58,17 +60,23 @@ for v in ([] if a.no_variants else [int(x) for x in a.variants.split(",")]):
         e1.record()
         e1.synchronize()
         print(f"variant {v} rounds {gr}: {e0.elapsed_time(e1) / a.reps:.5f} ms per launch", flush=True)
+qs = [int(x) for x in a.quotient.split(",")]
+Q = None
+if a.twostep and 1 in qs:
+    Q = torch.empty_like(Cp)
+    native.quotient(Q.data_ptr(), Cp.data_ptr(), Cp.numel(), 0.01, Cp.element_size(), s)
 for f in [int(x) for x in a.twostep.split(",") if x]:
     for gr in [int(x) for x in a.rounds.split(",")]:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            native.diffusion3d_twostep(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), [n, n, n], [1.0, 1.0, 1.0], 0.01,
-                                       T.element_size(), f, s, gr, a.halo_z)
-        e1.record()
-        e1.synchronize()
-        print(f"twostep form {f} rounds {gr}: {e0.elapsed_time(e1) / a.reps:.5f} ms per pass "
-              f"({e0.elapsed_time(e1) / a.reps / 2:.5f} per step)", flush=True)
+        for q in qs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                native.diffusion3d_twostep(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), [n, n, n], [1.0, 1.0, 1.0],
+                                           0.01, T.element_size(), f, s, gr, a.halo_z, Q.data_ptr() if q else 0)
+            e1.record()
+            e1.synchronize()
+            print(f"twostep form {f} rounds {gr}{' Q' if q else ''}: {e0.elapsed_time(e1) / a.reps:.5f} ms per pass "
+                  f"({e0.elapsed_time(e1) / a.reps / 2:.5f} per step)", flush=True)
 if a.calib:
     for _ in range(a.reps):
         T2.copy_(T)  # reads n^3 and writes n^3 elements

@@ -842,15 +842,22 @@ PYBIND11_MODULE(_igg_native, m) {
   // Two time steps in one pass (stencil2_kernels.hip): whole inner box, GPU only.
   m.def("diffusion3d_twostep",
         [](uintptr_t t2, uintptr_t t, uintptr_t cp, const Int3& n, const std::array<double, 3>& rd2,
-           double dtlam, int elem_bytes, int form, uintptr_t stream, int rounds, bool halo_z) {
+           double dtlam, int elem_bytes, int form, uintptr_t stream, int rounds, bool halo_z, uintptr_t q) {
           TraceRange tr("igg.diffusion3d_twostep");
           DiffusionArgs a{t2, t, cp, {n[0], n[1], n[2]}, {rd2[0], rd2[1], rd2[2]}, dtlam, elem_bytes, rounds, halo_z,
-                          form};
+                          form, q};
           launch_diffusion3d_twostep(a, as_stream(stream));
         },
         py::arg("t2"), py::arg("t"), py::arg("cp"), py::arg("n"), py::arg("rd2"), py::arg("dtlam"),
         py::arg("elem_bytes"), py::arg("form") = 0, py::arg("stream") = 0, py::arg("rounds") = 0,
-        py::arg("halo_z") = false);
+        py::arg("halo_z") = false, py::arg("q") = 0);
+  // q = dtlam / cp as the two-step pass divides (stencil2q_kernels.hip): its optional input `q`. GPU only.
+  m.def("quotient",
+        [](uintptr_t q, uintptr_t cp, int64_t n, double dtlam, int elem_bytes, uintptr_t stream) {
+          TraceRange tr("igg.quotient");
+          launch_quotient(q, cp, n, dtlam, elem_bytes, as_stream(stream));
+        },
+        py::arg("q"), py::arg("cp"), py::arg("n"), py::arg("dtlam"), py::arg("elem_bytes"), py::arg("stream") = 0);
   m.def("diffusion3d_twostep_ok",
         [](const Int3& n, int elem_bytes, int form) {
           DiffusionArgs a{0, 0, 0, {n[0], n[1], n[2]}, {1.0, 1.0, 1.0}, 0.0, elem_bytes, 0, false, form};

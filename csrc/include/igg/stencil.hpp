@@ -43,7 +43,15 @@ struct DiffusionArgs {
   // up to -2.9 % (profiles/r4_halo_z/).
   bool halo_z = false;
   int form = 0;             // two-step pass only: tiling (diffusion3d_twostep_num_forms)
+  // Two-step pass only: 0, or an array like cp that holds dt_lam/cp as
+  // launch_quotient leaves it; the pass then reads it where it reads cp
+  // (same bytes, no division) and leaves bitwise the same values.
+  uintptr_t q = 0;
 };
+
+// q = dt_lam / cp elementwise (n elements), the division of diffusion_point
+// under the build's flags: what the two-step pass computes per point itself.
+void launch_quotient(uintptr_t q, uintptr_t cp, int64_t n, double dt_lam, int elem_bytes, hipStream_t stream);
 
 // Number of tuned kernel variants (see stencil_kernels.hip); variant 0 = default.
 int diffusion3d_num_variants();

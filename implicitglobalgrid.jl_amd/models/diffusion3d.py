@@ -36,6 +36,7 @@ import warnings
 import torch
 
 from .. import parallel  # noqa: F401
+from .._native import IGGError
 from ..ops import stencil
 from ..parallel import grid as _grid
 from ..parallel.halo import update_halo_
@@ -83,6 +84,17 @@ class Diffusion3D(PingPongModel):
     single-step kernel: assigning another one than the selection ran with
     switches the pass off until the original is assigned back.
 
+    Quotient array (``Q``; IGG_STENCIL_QUOTIENT=auto|0|1): the pass may read
+    ``Q = dt*lam/Cp`` where it reads ``Cp`` and then does not divide (the same
+    bytes per pass, bitwise the same values). ``Cp``, ``dt`` and ``lam`` are
+    constant over a time loop, so the model owns one further array of the
+    fields' size (1 GiB at 512^3 float64; never checkpointed), builds it when
+    the pass is selected and rebuilds it in place at the entry of
+    ``run``/``capture`` when ``Cp`` (its storage or torch's version counter),
+    ``dt`` or ``lam`` changed; after a write to ``Cp`` that torch cannot see
+    (a raw pointer, another process) call ``mark_cp_modified()``. ``auto``
+    keeps it where the set-up A/B measures the pass faster with it.
+
     ``T2`` is the other ping-pong buffer: its boundary planes always equal
     ``T``'s fixed boundary values; its interior is the field of one step ago
     after a single step and of TWO steps ago after a two-step pass (it is
@@ -115,6 +127,10 @@ class Diffusion3D(PingPongModel):
         self.two_step_form = 0
         self.two_step_rounds = 0
         self.two_step_times = {}
+        # The pass's quotient array dt*lam/Cp (None: the pass reads Cp) and
+        # what it was built from (Cp's storage and version, dt*lam).
+        self.Q = None
+        self._q_key = None
         self.rounds = 0  # grid residency rounds of the full-interior launch (0: library default)
         self.halo_z = HALO_Z  # whole-line z-edge stores of the full-interior launch (autotuned per variant)
         self.variant_times = None  # per-variant ms when autotuned (see _choose_variant)
@@ -154,6 +170,7 @@ class Diffusion3D(PingPongModel):
             # csrc/vmm.cpp), which gather_ maps through a file descriptor at
             # any size instead of staging it in chunks (round 6).
             kinds = {"torch": None, "fine": 1, "vmm": 4}
+            self._field_kind = kinds[self.field_memory]
             spec = [torch.empty(shape, dtype=dtype, device="meta")] * 3
             multi = int(gg.nprocs) > 1
             big = multi and spec[0].numel() * spec[0].element_size() >= ipc_limit()
@@ -281,7 +298,39 @@ class Diffusion3D(PingPongModel):
         return _pass_halo_ok() and stencil.twostep_ok(self.T, self.two_step_form)
 
     def _pass_key(self):
-        return (self.two_step_form, self.two_step_rounds)
+        return (self.two_step_form, self.two_step_rounds, self.Q is not None)
+
+    def _alloc_q(self) -> None:
+        """The quotient array, in the fields' kind of memory (not yet built)."""
+        meta = torch.empty(self.T.shape, dtype=self.dtype, device="meta")
+        (self.Q,) = _carve([meta], gap=0, kind=self._field_kind, device=self.device)
+        self._q_key = None
+
+    def _refresh_q(self) -> None:
+        """Rebuild ``Q`` in place if what it was built from changed (the buffer
+        stays, so a captured graph that reads it stays valid)."""
+        if self.Q is None:
+            return
+        key = (self.Cp.data_ptr(), self.Cp._version, self.dt * self.lam)
+        if key != self._q_key:
+            stencil.quotient_(self.Q, self.Cp, lam=self.lam, dt=self.dt)
+            self._q_key = key
+
+    def mark_cp_modified(self) -> None:
+        """``Cp`` was written behind torch's back (a raw pointer, a kernel of
+        another library): the next ``run``/``capture`` rebuilds ``Q``."""
+        self._q_key = None
+
+    def run(self, nt: int) -> None:
+        self._refresh_q()
+        super().run(nt)
+
+    def capture(self, steps: int = None) -> None:
+        self._refresh_q()
+        super().capture(steps)
+
+    run.__doc__ = PingPongModel.run.__doc__
+    capture.__doc__ = PingPongModel.capture.__doc__
 
     def _swap(self) -> None:
         self.T, self.T2 = self.T2, self.T
@@ -295,7 +344,7 @@ class Diffusion3D(PingPongModel):
         (next to a physical boundary plane 0 is fixed, so plane 1 is exact)."""
         stencil.diffusion3d_twostep_(self.T2, self.T, self.Cp, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy,
                                      dz=self.dz, form=self.two_step_form, rounds=self.two_step_rounds,
-                                     halo_z=HALO_Z)
+                                     halo_z=HALO_Z, Q=self.Q)
         if exchanging_dims(3):
             update_halo_(self.T2)
         self._swap()
@@ -588,23 +637,47 @@ def _select_two_step(m: "Diffusion3D") -> None:
     choice: one that exchanged every step would mismatch one that exchanges
     every two), and the timing itself is collective."""
     env = two_step_env("IGG_STENCIL_TWOSTEP")
+    qenv = two_step_env("IGG_STENCIL_QUOTIENT")
     m.two_step = False
+    m.Q = None
     if env == "0" or m.device.type != "cuda" or m.variant is None or not _pass_halo_ok():
         return
     forms = [f for f in stencil.TWOSTEP_FORMS if stencil.twostep_ok(m.T, f)]
     if not forms:
         return
+    if qenv != "0":
+        # One more array of the fields' size; "auto" goes on without it where
+        # it does not fit, "1" raises.
+        try:
+            m._alloc_q()
+            m._refresh_q()
+        except (RuntimeError, IGGError):
+            m.Q = None
+            if qenv == "1":
+                raise
+        gg = _grid.global_grid()
+        if gg.nprocs > 1 and exchanging_dims(3):
+            # the A/B below is collective over the same candidates: all ranks with Q or none
+            import torch.distributed as dist
+
+            have = torch.tensor([int(m.Q is not None)])
+            dist.all_reduce(have, op=dist.ReduceOp.MIN, group=gg.comm.gloo)
+            if not int(have[0]):
+                m.Q = None
     if env == "1":
         m.two_step_form, m.two_step_rounds = forms[0], 0
         m.two_step = True
         return
     rd2 = [1.0 / m.dx ** 2, 1.0 / m.dy ** 2, 1.0 / m.dz ** 2]
     boxes = [(list(b[0]), list(b[1])) for b in m.inner]
-    cands = [(f, r, HALO_Z) for f in forms for r in stencil.GRID_ROUNDS]
+    # every pass candidate reading Cp and reading Q ("1": Q only), so that Q's
+    # placement in memory is part of what is measured
+    qs = [q for q in (False, True) if (q and m.Q is not None) or (not q and not (qenv == "1" and m.Q is not None))]
+    cands = [(f, r, HALO_Z, q) for f in forms for r in stencil.GRID_ROUNDS for q in qs]
     exchanging = bool(exchanging_dims(3))
     single, t = stencil.time_twostep_pingpong(m.T2, m.T, m.Cp, rd2, m.dt * m.lam, boxes,
                                               (int(m.variant), int(m.rounds), bool(m.halo_z)), cands,
-                                              exchange=update_halo_ if exchanging else None)
+                                              exchange=update_halo_ if exchanging else None, Q=m.Q)
     gg = _grid.global_grid()
     if exchanging and gg.nprocs > 1:
         import torch.distributed as dist
@@ -613,10 +686,12 @@ def _select_two_step(m: "Diffusion3D") -> None:
         dist.all_reduce(tot, group=gg.comm.gloo)
         tot /= int(gg.nprocs)
         single, t = float(tot[0]), {c: float(x) for c, x in zip(cands, tot[1:])}
-    best = faster_pass(m, single, t, lambda c: f"t{c[0]}@r{c[1]}")
+    best = faster_pass(m, single, t, lambda c: f"t{c[0]}{'q' if c[3] else ''}@r{c[1]}")
     if best is not None:
         m.two_step_form, m.two_step_rounds = int(best[0]), int(best[1])
         m.two_step = True
+    if best is None or not best[3]:
+        m.Q = None  # lost the A/B: the array is freed
 
 
 def _hw_queues() -> int | None:

@@ -203,30 +203,62 @@ def twostep_ok(T, form: int = 0) -> bool:
 
 
 def diffusion3d_twostep_(T2, T, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: float,
-                         form: int = 0, rounds: int = 0, halo_z: bool = False, stream: int | None = None) -> None:
+                         form: int = 0, rounds: int = 0, halo_z: bool = False, stream: int | None = None,
+                         Q=None) -> None:
     """Two diffusion updates in one pass over memory: afterwards ``T2`` holds,
     bitwise, what ``diffusion3d_(tmp, T, Cp)`` then ``diffusion3d_(T2, tmp, Cp)``
     on the whole interior leave, where ``tmp``'s boundary planes equal ``T``'s
     (fixed boundary values, no halo exchange between the two steps). ``T`` and
     ``Cp`` are only read; ``T2``'s boundary planes are not written (``halo_z``
     as in ``diffusion3d_``). GPU only; raises ``IGGError`` where ``twostep_ok``
-    is false (callers then run two single steps)."""
+    is false (callers then run two single steps).
+
+    ``Q``: optionally the array ``quotient_`` left for this ``Cp`` and
+    ``dt * lam`` (same shape, dtype and device as ``Cp``). The pass then reads
+    it where it reads ``Cp`` and does not divide; the result is bitwise the
+    same. Keeping ``Q`` current when ``Cp``, ``dt`` or ``lam`` change is the
+    caller's business."""
     _check(T2, T, Cp)
     if not T.is_cuda:
         raise IGGError("diffusion3d_twostep: GPU tensors only (there is no host two-step kernel)")
     if not twostep_ok(T, form):
         raise IGGError(f"diffusion3d_twostep: form {form} cannot run shape {tuple(T.shape)} {T.dtype}")
+    if Q is not None:
+        _check_q(Q, Cp)
     rd2 = [1.0 / (dx * dx), 1.0 / (dy * dy), 1.0 / (dz * dz)]
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     native.diffusion3d_twostep(T2.data_ptr(), T.data_ptr(), Cp.data_ptr(), list(T.shape), rd2, dt * lam,
-                               T.element_size(), int(form), s, int(rounds), bool(halo_z))
+                               T.element_size(), int(form), s, int(rounds), bool(halo_z),
+                               0 if Q is None else Q.data_ptr())
+
+
+def _check_q(Q, Cp) -> None:
+    if Q.shape != Cp.shape or Q.dtype != Cp.dtype or not Q.is_contiguous() or not Cp.is_contiguous():
+        raise IGGError(f"quotient: Q {tuple(Q.shape)} {Q.dtype} must match Cp {tuple(Cp.shape)} {Cp.dtype}, "
+                       "both C-contiguous")
+    if not (Q.is_cuda and Q.device == Cp.device):
+        raise IGGError("quotient: Q must be a GPU tensor on Cp's device")
+    if Q.data_ptr() == Cp.data_ptr():
+        raise IGGError("quotient: Q aliases Cp")
+
+
+def quotient_(Q, Cp, *, lam: float, dt: float, stream: int | None = None) -> None:
+    """``Q = dt*lam / Cp`` elementwise, by the division of the diffusion
+    kernels: the optional input ``Q`` of ``diffusion3d_twostep_``. GPU only,
+    float32 / float64."""
+    if not Cp.is_cuda or Cp.dtype not in (torch.float32, torch.float64):
+        raise IGGError("quotient: float32 / float64 GPU tensors only")
+    _check_q(Q, Cp)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    native.quotient(Q.data_ptr(), Cp.data_ptr(), Cp.numel(), dt * lam, Cp.element_size(), s)
 
 
 def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, steps: int = 20, rounds: int = 5,
-                          exchange=None) -> tuple:
+                          exchange=None, Q=None) -> tuple:
     """Median ms PER STEP of the single-step candidate ``single`` (a
     (variant, rounds, halo_z) triple) and of each two-step candidate (form,
-    rounds, halo_z), interleaved, in the time loop's ping-pong shape on the
+    rounds, halo_z) or (form, rounds, halo_z, use_q) - use_q: the pass reads
+    the quotient array ``Q`` (``quotient_``) -, interleaved, in the time loop's ping-pong shape on the
     model's own two buffers (``steps`` a multiple of 4: an even number of
     passes). T is saved and restored; T2's interior is scribbled. With
     ``exchange`` (``update_halo_`` on a grid whose halo is two planes deep) it
@@ -242,9 +274,10 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
             if c is None:
                 launch(single, dst, src)
             else:
-                f, gr, hz = c
+                f, gr, hz = c[:3]
+                q = Q if len(c) > 3 and c[3] else None
                 native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f, s, gr,
-                                           hz)
+                                           hz, 0 if q is None else q.data_ptr())
             if exchange is not None:
                 exchange(dst)
 

@@ -23,6 +23,10 @@ nodes; parallel/transport_select.py); ``put`` = one-sided IPC stores over xGMI
 gloo, the reference's non-GPU-aware path. Also ``IGG_STENCIL_VARIANT`` (int or
 ``auto``), ``IGG_STENCIL_TWOSTEP`` (``auto`` | ``0`` | ``1``: the diffusion model's
 two-steps-per-pass kernel on a rank without neighbours),
+``IGG_STENCIL_QUOTIENT`` (``auto`` | ``0`` | ``1``: that pass reads a quotient
+array ``dt*lam/Cp`` the model keeps - one more array of the fields' size -
+instead of dividing; ``auto`` keeps it where the set-up timing finds the pass
+faster with it, and means on where ``IGG_STENCIL_TWOSTEP=1`` skips the timing),
 ``IGG_ACOUSTIC_TWOSTEP`` (the same for the acoustic model), ``IGG_DEBUG_SYNC`` (synchronise after every halo update), ``IGG_QUIET``.
 """
 from __future__ import annotations

@@ -6,7 +6,8 @@ object that ``tools/kernel_resources.py`` unbundles), finds its loops (every
 backward branch closes one: [target, branch]) and counts, per loop, the
 instruction classes that decide a memory-bound sweep's issue budget: VALU,
 cross-lane moves (``v_readlane``/``v_writelane``: also what SGPR spills
-compile to), AGPR copies (``v_accvgpr_*``: what VGPR pressure above the 256
+compile to), register moves, the division sequence, 64-bit per-lane address
+arithmetic, scalar multiplies and exec-mask regions, AGPR copies (``v_accvgpr_*``: what VGPR pressure above the 256
 arch VGPRs compiles to), selects, scratch, vector memory and LDS. The x-march
 loop of each per-wave sweep form of the fused kernel is one of the large
 loops, so the per-form cost of the exchange can be read without a GPU.
@@ -32,10 +33,15 @@ CLASSES = (
     ("writelane", lambda m: m.startswith("v_writelane")),
     ("accvgpr", lambda m: m.startswith("v_accvgpr")),
     ("cndmask", lambda m: m.startswith("v_cndmask")),
+    ("mov", lambda m: m.startswith("v_mov_b")),
+    ("division", lambda m: m.startswith(("v_div_scale", "v_div_fmas", "v_div_fixup", "v_rcp_f"))),
+    ("addr64", lambda m: m.startswith(("v_lshl_add_u64", "v_mad_u64_u32", "v_mad_i64_i32", "v_addc_co"))),
     ("fp64", lambda m: m.endswith("_f64") or "_f64_" in m),
     ("valu", lambda m: m.startswith("v_")),
     ("salu", lambda m: m.startswith("s_") and not m.startswith(("s_load", "s_buffer", "s_waitcnt", "s_cbranch",
                                                                    "s_branch", "s_nop"))),
+    ("s_mul", lambda m: m.startswith("s_mul_")),
+    ("saveexec", lambda m: "saveexec" in m),
     ("smem", lambda m: m.startswith(("s_load", "s_buffer_load"))),
     ("vmem_load", lambda m: m.startswith(("global_load", "buffer_load", "flat_load"))),
     ("vmem_store", lambda m: m.startswith(("global_store", "buffer_store", "flat_store"))),
