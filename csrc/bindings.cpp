@@ -25,6 +25,7 @@
 #include "igg/gather.hpp"
 #include "igg/halo.hpp"
 #include "igg/ipc.hpp"
+#include "igg/reduce.hpp"
 #include "igg/stencil.hpp"
 #include "igg/topology.hpp"
 #include "igg/trace.hpp"
@@ -485,6 +486,59 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("box"), py::arg("ptrs"), py::arg("elem_bytes"),
         "What launch_copy3d does with one box: the normalised box (extents, src strides, dst strides), path "
         "(flat / gather / chunk), vec_bytes (0, 4, 8 or 16) and blocks.");
+
+  // --- reductions (ops/reduce.py)
+  m.attr("REDUCE_MAX_BLOCKS") = REDUCE_MAX_BLOCKS;
+  m.attr("REDUCE_MAX_JOBS") = REDUCE_MAX_JOBS;
+  m.attr("REDUCE_UNROLL") = REDUCE_UNROLL;
+  m.def("reduce_plan",
+        [](const std::vector<int64_t>& shape, const std::vector<int64_t>& strides, const std::vector<int64_t>& lo,
+           const std::vector<int64_t>& hi, int elem_size, uintptr_t base_address,
+           const std::vector<int64_t>& strides_b, uintptr_t base_b) {
+          const ReducePlan p = plan_reduce(shape, strides, lo, hi, elem_size, base_address, strides_b, base_b);
+          py::dict d;
+          d["path"] = reduce_path_name(p.path);
+          d["box"] = py::make_tuple(p.n[0], p.n[1], p.n[2]);
+          d["strides"] = py::make_tuple(p.s[0], p.s[1], p.s[2]);
+          d["offset"] = p.offset;
+          d["total"] = p.total;
+          d["vec"] = p.vec;
+          d["head"] = p.head;
+          d["loads_per_row"] = p.nv;
+          d["lanes_per_row"] = int64_t{1} << p.lx_log2;
+          d["tiles"] = p.tiles;
+          d["blocks"] = p.blocks;
+          return d;
+        },
+        py::arg("shape"), py::arg("strides"), py::arg("lo"), py::arg("hi"), py::arg("elem_size"),
+        py::arg("base_address"), py::arg("strides_b") = std::vector<int64_t>{}, py::arg("base_b") = 0,
+        "What a reduction does with the box [lo, hi) of one field: the merged box (extents, strides in elements), "
+        "path (flat / rows / element), elements per load, head mask, tiles and blocks.");
+  m.def("reduce",
+        [](int op,
+           const std::vector<std::tuple<uintptr_t, uintptr_t, std::vector<int64_t>, std::vector<int64_t>,
+                                        std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>>>& fields,
+           int elem_size, uintptr_t out, uintptr_t flags, uintptr_t stream) {
+          std::vector<ReduceField> fs;
+          fs.reserve(fields.size());
+          for (const auto& t : fields) {
+            ReduceField f;
+            f.a = std::get<0>(t), f.b = std::get<1>(t);
+            f.shape = std::get<2>(t), f.stride_a = std::get<3>(t), f.stride_b = std::get<4>(t);
+            f.lo = std::get<5>(t), f.hi = std::get<6>(t);
+            fs.push_back(std::move(f));
+          }
+          reduce_fields(op, fs, elem_size, reinterpret_cast<double*>(out), reinterpret_cast<double*>(flags),
+                        as_stream(stream));
+        },
+        py::arg("op"), py::arg("fields"), py::arg("elem_size"), py::arg("out"), py::arg("flags") = 0,
+        py::arg("stream") = 0,
+        "out[k] (f64, device) = op over the box of field k: fields are (a, b, shape, strides_a, strides_b, lo, hi), "
+        "ops 0 sum, 1 sumsq, 2 max, 3 min, 4 maxabs, 5 dot, 6 sumsq_diff, 7 maxabs_diff. With `flags` the max-type "
+        "ops write the travel form: value with NaN as -inf (min: of -x) and a NaN flag.");
+  m.def("reduce_workspace_bytes", &reduce_workspace_bytes, "Bytes of the reductions' device workspaces.");
+  m.def("reduce_free_workspace", &reduce_free_workspace,
+        "Free the reductions' workspaces (one device synchronisation each); finalize_global_grid calls it.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

@@ -30,13 +30,16 @@ def main():
     igg.tic()
     model.run(a.nt)
     t = igg.toc()
-    # Global maximum over the ranks through the grid's communicator (the
-    # reference apps call MPI.Allreduce on comm_cart for such diagnostics).
-    t_max = comm.allreduce_(model.T.max().reshape(1).clone(), "max")
+    # Global maximum and mean: reductions over the global grid in which every
+    # global cell counts once (the reference apps call MPI.Allreduce on
+    # comm_cart themselves, which double counts the overlaps in a sum).
+    t_max = igg.max_g(model.T)
+    t_mean = igg.mean_g(model.T)
     if me == 0:
         t_it = t / a.nt
         print(f"{nprocs} process(es) {dims.tolist()}: {t:.3f} s, {t_it * 1e3:.3f} ms/step, "
-              f"T_eff = {t_eff_gbs(model, t_it):.2f} GB/s per process, global T_max = {float(t_max):.6f}")
+              f"T_eff = {t_eff_gbs(model, t_it):.2f} GB/s per process, global T_max = {float(t_max):.6f}, "
+              f"global T_mean = {float(t_mean):.6f}")
     igg.finalize_global_grid()
 
 

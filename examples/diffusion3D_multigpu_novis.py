@@ -40,12 +40,13 @@ def main():
     t = igg.toc()
     model.sync_halo()                                                        # halos of T valid again (fused mode)
     model.close()
-    t_max = comm.allreduce_(model.T.max().reshape(1).clone(), "max")        # global max (RCCL, on the stream)
+    t_max = igg.max_g(model.T)                                               # global max (HIP reduction + RCCL)
+    t_mean = igg.mean_g(model.T)                                             # every global cell counted once
     if me == 0:
         t_it = t / a.nt
         print(f"{nprocs} process(es) {dims.tolist()}, local {a.nx}^3, global {igg.nx_g()}x{igg.ny_g()}x{igg.nz_g()}: "
               f"{t:.3f} s, {t_it * 1e3:.4f} ms/step, T_eff = {t_eff_gbs(model, t_it):.1f} GB/s per GPU, "
-              f"global T_max = {float(t_max):.6f}")
+              f"global T_max = {float(t_max):.6f}, global T_mean = {float(t_mean):.6f}")
     igg.finalize_global_grid()                                               # Finalize the implicit global grid
 
 

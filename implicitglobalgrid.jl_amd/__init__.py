@@ -11,7 +11,9 @@ Public API (reference names in parentheses, src/ImplicitGlobalGrid.jl:9-23):
 ``init_global_grid``, ``finalize_global_grid``, ``update_halo_``
 (``update_halo!``), ``gather_`` (``gather!``), ``select_device``, ``nx_g``,
 ``ny_g``, ``nz_g``, ``x_g``, ``y_g``, ``z_g``, ``tic``, ``toc`` and
-``get_global_grid``.
+``get_global_grid``. Beyond the reference: reductions over the global grid in
+which every global cell counts once (``reduce_g``, ``sum_g``, ``norm_g``,
+``max_g``, ``mean_g``, ...; ops/reduce.py).
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -28,6 +30,20 @@ from .parallel.transport_select import select_transport  # noqa: F401
 from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
 from .utils.tools import coords_g, nx_g, ny_g, nz_g, tic, toc, x_g, y_g, z_g  # noqa: F401
 from .utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
+from .ops.reduce import (  # noqa: F401
+    dot_g,
+    max_g,
+    maxabs_diff_g,
+    maxabs_g,
+    mean_g,
+    min_g,
+    norm_diff_g,
+    norm_g,
+    owned_ranges,
+    owned_view,
+    reduce_g,
+    sum_g,
+)
 
 __version__ = "0.1.0"
 
@@ -35,4 +51,6 @@ __all__ = [
     "init_global_grid", "finalize_global_grid", "update_halo_", "update_halo", "gather_", "gather",
     "select_device", "nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "tic", "toc", "get_global_grid",
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
+    "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
+    "norm_g", "norm_diff_g", "mean_g",
 ]

@@ -167,6 +167,47 @@ class PingPongModel:
         if ran:
             self._drain()
 
+    def _residual(self) -> torch.Tensor:
+        """The change of the model's field over the LAST SINGLE step, reduced
+        over the global grid (a device scalar; ops.reduce). Models with a
+        steady state supply it."""
+        raise NotImplementedError(f"{type(self).__name__} has no steady state: no residual, no run_until")
+
+    def run_until(self, tol: float, max_steps: int, check_every: int = None) -> tuple:
+        """Advance until the residual falls below ``tol`` or ``max_steps``
+        steps ran; returns ``(steps, residual)`` (collective: every rank gets
+        the same residual and stops at the same step).
+
+        The steps run in blocks of ``check_every``: ``run(check_every - 1)``,
+        then one ``step()``, then ONE host read of the residual. After a
+        two-step pass the other buffer is two steps old and the residual must
+        be the change over one step, so a block ends in a single ``step()``.
+        ``check_every`` defaults to ``graph_steps + 1`` with a captured graph
+        and ``GRAPH_STEPS + 1`` without: a block is one replay plus one step.
+        (The odd block length hands the buffers to every other block swapped,
+        and that block's ``run`` goes eagerly; ``check_every = graph_steps + 2``
+        keeps every block on the graph.) The last block is shortened so that
+        ``steps`` never exceeds ``max_steps``; ``run_until(0.0, N)`` leaves
+        the field bitwise as ``run(N)`` does."""
+        if type(self)._residual is PingPongModel._residual:
+            self._residual()  # raises
+        max_steps = int(max_steps)
+        if check_every is None:
+            check_every = (self.graph_steps if self.graph is not None else GRAPH_STEPS) + 1
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError(f"{type(self).__name__}.run_until: check_every must be at least 1")
+        steps, residual = 0, float("inf")
+        while steps < max_steps:
+            k = min(check_every, max_steps - steps)
+            self.run(k - 1)
+            self.step()
+            steps += k
+            residual = float(self._residual().item())
+            if residual < tol:
+                break
+        return steps, residual
+
     def save(self, prefix: str, step: int = 0) -> str:
         """Per-rank checkpoint of the model state (collective; utils.checkpoint).
         Materialises fused-mode halos first (``sync_halo``), so the files hold

@@ -335,6 +335,19 @@ class Diffusion3D(PingPongModel):
     def _swap(self) -> None:
         self.T, self.T2 = self.T2, self.T
 
+    def residual(self) -> torch.Tensor:
+        """``max|T - T2|`` over the global grid as a device scalar
+        (``maxabs_diff_g``): right after a single ``step()`` the largest change
+        of the step. It reads owned cells only, none of them a halo plane, so
+        it is valid in fused mode without ``sync_halo()``. (After ``run`` the
+        last pass may have been a two-step pass and ``T2`` two steps old: take
+        one ``step()`` first, as ``run_until`` does.)"""
+        from ..ops.reduce import maxabs_diff_g
+
+        return maxabs_diff_g(self.T, self.T2)
+
+    _residual = residual
+
     def _pass(self) -> None:
         """Two time steps in one pass (callers checked ``_two_step_now``), then
         the exchange of the two halo planes per side the next pass reads. The

@@ -311,5 +311,6 @@ def finalize_global_grid(*, finalize_MPI: bool = True) -> None:
         from .._native import native
 
         native.flush_deferred_frees()  # native field buffers released by the collection
+        native.reduce_free_workspace()  # the global reductions' partials (ops/reduce.py)
     if transport_error is not None:
         raise transport_error
