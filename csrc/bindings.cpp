@@ -26,6 +26,7 @@
 #include "igg/halo.hpp"
 #include "igg/ipc.hpp"
 #include "igg/reduce.hpp"
+#include "igg/select.hpp"
 #include "igg/stencil.hpp"
 #include "igg/topology.hpp"
 #include "igg/trace.hpp"
@@ -540,11 +541,65 @@ PYBIND11_MODULE(_igg_native, m) {
   m.def("reduce_free_workspace", &reduce_free_workspace,
         "Free the reductions' workspaces (one device synchronisation each); finalize_global_grid calls it.");
 
+  // --- converting lattice copy (parallel/gather_g.py)
+  m.attr("SELECT_MAX_BLOCKS") = SELECT_MAX_BLOCKS;
+  m.attr("SELECT_MAX_JOBS") = SELECT_MAX_JOBS;
+  m.def("select_plan",
+        [](const std::array<int64_t, 3>& counts, const std::array<int64_t, 3>& src_strides,
+           const std::array<int64_t, 3>& dst_strides) {
+          const SelectPlan p = plan_select(counts.data(), src_strides.data(), dst_strides.data());
+          py::dict d;
+          d["path"] = select_path_name(p.path);
+          d["index_bits"] = p.index_bits;
+          d["total"] = p.total;
+          d["rows"] = p.rows;
+          d["src_span"] = p.src_span;
+          d["dst_span"] = p.dst_span;
+          d["blocks"] = p.blocks;
+          return d;
+        },
+        py::arg("counts"), py::arg("src_strides"), py::arg("dst_strides"),
+        "What select_convert does with one job (counts and strides in elements, outer .. inner): path (rows / "
+        "element), index_bits (32 / 64), elements, rows, spans and blocks (0: empty, skipped).");
+  m.def("select_convert",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, std::array<int64_t, 3>, std::array<int64_t, 3>,
+                                        std::array<int64_t, 3>>>& jobs,
+           uintptr_t stream) {
+          std::vector<SelectDesc> v;
+          v.reserve(jobs.size());
+          for (const auto& t : jobs) {
+            SelectDesc j;
+            j.src = std::get<0>(t), j.dst = std::get<1>(t);
+            for (int d = 0; d < 3; ++d)
+              j.c[d] = std::get<2>(t)[d], j.S[d] = std::get<3>(t)[d], j.T[d] = std::get<4>(t)[d];
+            v.push_back(j);
+          }
+          select_convert(v, as_stream(stream));
+        },
+        py::arg("jobs"), py::arg("stream") = 0,
+        "dst[i0*T0 + i1*T1 + i2*T2] (f32, device) = float(src[i0*S0 + i1*S1 + i2*S2]) (f64, device), i_d < c_d, for "
+        "every job (src, dst, counts, src strides, dst strides); strides in elements.");
+
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")
       .def_property_readonly("name", &Transport::name)
       .def_property_readonly("device_capable", &Transport::device_capable)
-      .def_property_readonly("host_capable", &Transport::host_capable);
+      .def_property_readonly("host_capable", &Transport::host_capable)
+      .def("exchange",
+           [](Transport& t, const std::vector<std::tuple<uintptr_t, size_t, int, int>>& recvs,
+              const std::vector<std::tuple<uintptr_t, size_t, int, int>>& sends, bool device, uintptr_t s) {
+             auto conv = [](const std::vector<std::tuple<uintptr_t, size_t, int, int>>& ops) {
+               std::vector<P2POp> v;
+               v.reserve(ops.size());
+               for (const auto& x : ops)
+                 v.push_back({reinterpret_cast<void*>(std::get<0>(x)), std::get<1>(x), std::get<2>(x), std::get<3>(x)});
+               return v;
+             };
+             t.exchange(conv(recvs), conv(sends), device, as_stream(s));
+           },
+           py::arg("recvs"), py::arg("sends"), py::arg("device"), py::arg("stream") = 0,
+           "One point-to-point phase: every receive, then every send, as (pointer, bytes, peer, tag); messages may "
+           "have any, unequal sizes. Device memory is ordered on `stream`.");
   py::class_<PyTransport, Transport, std::shared_ptr<PyTransport>>(m, "PyTransport")
       .def(py::init<py::function, bool, bool, std::string>(), py::arg("fn"), py::arg("host"),
            py::arg("device"), py::arg("name"));

@@ -13,7 +13,9 @@ Public API (reference names in parentheses, src/ImplicitGlobalGrid.jl:9-23):
 ``ny_g``, ``nz_g``, ``x_g``, ``y_g``, ``z_g``, ``tic``, ``toc`` and
 ``get_global_grid``. Beyond the reference: reductions over the global grid in
 which every global cell counts once (``reduce_g``, ``sum_g``, ``norm_g``,
-``max_g``, ``mean_g``, ...; ops/reduce.py).
+``max_g``, ``mean_g``, ...; ops/reduce.py) and ``gather_g``, which assembles
+the true global field - whole, a box of it or every n-th cell - from the owned
+cells (``indices_g``, ``selection_shape_g``; parallel/gather_g.py).
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -28,6 +30,7 @@ from .parallel.device import select_device  # noqa: F401
 from .parallel.halo import update_halo, update_halo_  # noqa: F401
 from .parallel.transport_select import select_transport  # noqa: F401
 from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
+from .parallel.gather_g import gather_g, indices_g, selection_shape_g  # noqa: F401
 from .utils.tools import coords_g, nx_g, ny_g, nz_g, tic, toc, x_g, y_g, z_g  # noqa: F401
 from .utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .ops.reduce import (  # noqa: F401
@@ -52,5 +55,5 @@ __all__ = [
     "select_device", "nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "tic", "toc", "get_global_grid",
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
-    "norm_g", "norm_diff_g", "mean_g",
+    "norm_g", "norm_diff_g", "mean_g", "gather_g", "indices_g", "selection_shape_g",
 ]

@@ -37,6 +37,9 @@ _sync_puller = None  # native PullGatherer of the synchronous gather_ (pull path
 
 def free_gather_buffer() -> None:
     global _host_buf, _gatherer, _puller, _sync_puller
+    from . import gather_g as _gather_g
+
+    _gather_g.free_buffers()
     _host_buf = None
     if _gatherer is not None:
         _gatherer.free()
