@@ -25,6 +25,7 @@
 #include "igg/gather.hpp"
 #include "igg/halo.hpp"
 #include "igg/ipc.hpp"
+#include "igg/project.hpp"
 #include "igg/reduce.hpp"
 #include "igg/select.hpp"
 #include "igg/stencil.hpp"
@@ -540,6 +541,69 @@ PYBIND11_MODULE(_igg_native, m) {
   m.def("reduce_workspace_bytes", &reduce_workspace_bytes, "Bytes of the reductions' device workspaces.");
   m.def("reduce_free_workspace", &reduce_free_workspace,
         "Free the reductions' workspaces (one device synchronisation each); finalize_global_grid calls it.");
+
+  // --- projections (ops/reduce.py project_g)
+  m.attr("PROJECT_MAX_BLOCKS") = PROJECT_MAX_BLOCKS;
+  m.attr("PROJECT_MAX_SLICES") = PROJECT_MAX_SLICES;
+  m.def("project_plan",
+        [](const std::vector<int64_t>& shape, const std::vector<int64_t>& strides, const std::vector<int64_t>& lo,
+           const std::vector<int64_t>& hi, const std::vector<int>& keep, int elem_size, uintptr_t base_address,
+           const std::vector<int64_t>& strides_b, uintptr_t base_b) {
+          const ProjectPlan p = plan_project(shape, strides, lo, hi, keep, elem_size, base_address, strides_b, base_b);
+          py::dict d;
+          d["family"] = p.family;
+          d["path"] = p.vector ? "vector" : "element";
+          d["pattern"] = std::string(p.pattern);
+          d["box"] = py::make_tuple(p.n[0], p.n[1], p.n[2], p.n[3]);
+          d["strides"] = py::make_tuple(p.s[0], p.s[1], p.s[2], p.s[3]);
+          d["offset"] = p.offset;
+          d["total"] = p.total;
+          d["outputs"] = p.nout;
+          d["vec"] = p.vec;
+          d["head"] = p.head;
+          d["loads_per_row"] = p.nv;
+          d["lanes"] = int64_t{1} << p.lanes_log2;
+          d["chunks_per_row"] = p.cx;
+          d["reduced"] = p.reduced;
+          d["slices"] = p.slices;
+          d["units"] = p.units;
+          d["block_units"] = p.block_units;
+          d["blocks"] = p.blocks;
+          d["index_bits"] = p.index_bits;
+          py::list ps;
+          for (int k = 0; k < p.nkeep; ++k) ps.append(p.keep_pstride[k]);
+          d["partial_strides"] = py::tuple(ps);
+          return d;
+        },
+        py::arg("shape"), py::arg("strides"), py::arg("lo"), py::arg("hi"), py::arg("keep"), py::arg("elem_size"),
+        py::arg("base_address"), py::arg("strides_b") = std::vector<int64_t>{}, py::arg("base_b") = 0,
+        "What a projection does with the box [lo, hi) of one field that keeps the axes `keep`: family (1 inner axis "
+        "kept, 2 inner axis reduced), path (vector / element), the merged pattern (outer .. inner, K kept, R "
+        "reduced), the extents and strides of the family's slots ([KO, R0, R1, KI] or [K0, K1, RO, RI]), elements "
+        "per load, head mask, lanes along a row, slices, units, blocks, the width of the loop offsets and the "
+        "stride of each kept axis in an output's partial index.");
+  m.def("project",
+        [](int op, uintptr_t a, uintptr_t b, const std::vector<int64_t>& shape, const std::vector<int64_t>& strides_a,
+           const std::vector<int64_t>& strides_b, const std::vector<int64_t>& lo, const std::vector<int64_t>& hi,
+           const std::vector<int>& keep, int elem_size, uintptr_t dst, uintptr_t flags,
+           const std::vector<int64_t>& dst_start, const std::vector<int64_t>& dst_extent,
+           const std::vector<int64_t>& dst_stride, uintptr_t stream) {
+          ReduceField f;
+          f.a = a, f.b = b, f.shape = shape, f.stride_a = strides_a, f.stride_b = strides_b, f.lo = lo, f.hi = hi;
+          ProjectDest d;
+          d.dst = dst, d.flags = flags, d.start = dst_start, d.extent = dst_extent, d.stride = dst_stride;
+          project_field(op, f, keep, elem_size, d, as_stream(stream));
+        },
+        py::arg("op"), py::arg("a"), py::arg("b"), py::arg("shape"), py::arg("strides_a"), py::arg("strides_b"),
+        py::arg("lo"), py::arg("hi"), py::arg("keep"), py::arg("elem_size"), py::arg("dst"), py::arg("flags"),
+        py::arg("dst_start"), py::arg("dst_extent"), py::arg("dst_stride"), py::arg("stream") = 0,
+        "dst (f64, device) = op over the axes of the box [lo, hi) that `keep` does not name (ops as in reduce). The "
+        "destination has dst_extent cells per kept axis at dst_stride (elements); the box's index i of a kept axis "
+        "lands at (dst_start + i) mod dst_extent, every other cell takes the op's identity. With `flags` (same "
+        "layout) the max-type ops write the travel form: value with NaN as -inf (min: of -x) and a NaN flag.");
+  m.def("project_workspace_bytes", &project_workspace_bytes, "Bytes of the projections' device workspaces.");
+  m.def("project_free_workspace", &project_free_workspace,
+        "Free the projections' workspaces (one device synchronisation each); finalize_global_grid calls it.");
 
   // --- converting lattice copy (parallel/gather_g.py)
   m.attr("SELECT_MAX_BLOCKS") = SELECT_MAX_BLOCKS;

@@ -13,9 +13,11 @@ Public API (reference names in parentheses, src/ImplicitGlobalGrid.jl:9-23):
 ``ny_g``, ``nz_g``, ``x_g``, ``y_g``, ``z_g``, ``tic``, ``toc`` and
 ``get_global_grid``. Beyond the reference: reductions over the global grid in
 which every global cell counts once (``reduce_g``, ``sum_g``, ``norm_g``,
-``max_g``, ``mean_g``, ...; ops/reduce.py) and ``gather_g``, which assembles
-the true global field - whole, a box of it or every n-th cell - from the owned
-cells (``indices_g``, ``selection_shape_g``; parallel/gather_g.py).
+``max_g``, ``mean_g``, ...; ops/reduce.py), ``project_g``, which reduces
+over some axes and keeps the others (profiles, column maxima), and
+``gather_g``, which assembles the true global field - whole, a box of it or
+every n-th cell - from the owned cells (``indices_g``, ``selection_shape_g``;
+parallel/gather_g.py).
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -44,6 +46,7 @@ from .ops.reduce import (  # noqa: F401
     norm_g,
     owned_ranges,
     owned_view,
+    project_g,
     reduce_g,
     sum_g,
 )
@@ -55,5 +58,5 @@ __all__ = [
     "select_device", "nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "tic", "toc", "get_global_grid",
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
-    "norm_g", "norm_diff_g", "mean_g", "gather_g", "indices_g", "selection_shape_g",
+    "norm_g", "norm_diff_g", "mean_g", "project_g", "gather_g", "indices_g", "selection_shape_g",
 ]

@@ -312,5 +312,6 @@ def finalize_global_grid(*, finalize_MPI: bool = True) -> None:
 
         native.flush_deferred_frees()  # native field buffers released by the collection
         native.reduce_free_workspace()  # the global reductions' partials (ops/reduce.py)
+        native.project_free_workspace()  # and the projections'
     if transport_error is not None:
         raise transport_error

@@ -25,7 +25,7 @@ SECTIONS = [
      ["nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "coords_g", "tic", "toc"]),
     ("Global reductions", "igg",
      ["owned_ranges", "owned_view", "reduce_g", "sum_g", "mean_g", "norm_g", "norm_diff_g", "dot_g", "max_g", "min_g",
-      "maxabs_g", "maxabs_diff_g"]),
+      "maxabs_g", "maxabs_diff_g", "project_g"]),
     ("Checkpoint / restart", "igg", ["save_checkpoint", "load_checkpoint"]),
     ("Halo engine knobs", "igg.parallel.halo",
      ["set_transport", "transport_name", "tuned_transports", "set_halo_mode", "halo_mode", "set_pack_mode",
