@@ -1042,6 +1042,30 @@ PYBIND11_MODULE(_igg_native, m) {
     for (int i = 0; i < diffusion3d_twostep_num_forms(); ++i) v.push_back(diffusion3d_twostep_form_name(i));
     return v;
   });
+  // Three time steps in one pass (stencil3_kernels.hip): rows within a tile, reads q. GPU only.
+  m.def("diffusion3d_threestep",
+        [](uintptr_t t2, uintptr_t t, uintptr_t q, const Int3& n, const std::array<double, 3>& rd2, double dtlam,
+           int elem_bytes, int form, uintptr_t stream, int rounds, bool halo_z) {
+          TraceRange tr("igg.diffusion3d_threestep");
+          DiffusionArgs a{t2, t, 0, {n[0], n[1], n[2]}, {rd2[0], rd2[1], rd2[2]}, dtlam, elem_bytes, rounds, halo_z,
+                          form, q};
+          launch_diffusion3d_threestep(a, as_stream(stream));
+        },
+        py::arg("t2"), py::arg("t"), py::arg("q"), py::arg("n"), py::arg("rd2"), py::arg("dtlam"),
+        py::arg("elem_bytes"), py::arg("form") = 0, py::arg("stream") = 0, py::arg("rounds") = 0,
+        py::arg("halo_z") = false);
+  m.def("diffusion3d_threestep_ok",
+        [](const Int3& n, int elem_bytes, int form) {
+          // (the quotient array: any non-null value, the shape is what is asked about)
+          DiffusionArgs a{0, 0, 0, {n[0], n[1], n[2]}, {1.0, 1.0, 1.0}, 0.0, elem_bytes, 0, false, form, 1};
+          return diffusion3d_threestep_ok(a);
+        },
+        py::arg("n"), py::arg("elem_bytes"), py::arg("form") = 0);
+  m.def("diffusion3d_threestep_forms", []() {
+    std::vector<std::string> v;
+    for (int i = 0; i < diffusion3d_threestep_num_forms(); ++i) v.push_back(diffusion3d_threestep_form_name(i));
+    return v;
+  });
   m.def("diffusion3d_fused_variant_ok", &diffusion3d_fused_variant_ok);
   m.def("diffusion3d_variant_compiled", &stencil_variant_compiled,
         "Whether stencil variant v is compiled in this build (measurement-only ones: build.py --probes).");

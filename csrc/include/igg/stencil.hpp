@@ -84,6 +84,18 @@ const char* diffusion3d_twostep_form_name(int form);
 bool diffusion3d_twostep_ok(const DiffusionArgs& a);
 void launch_diffusion3d_twostep(const DiffusionArgs& a, hipStream_t stream);
 
+// Three time steps in one pass over memory (stencil3_kernels.hip), in the
+// terms of the two-step pass: bitwise what three launch_diffusion3d calls
+// t -> tmp1 -> tmp2 -> t2 leave, both tmp's boundary planes being t's. Only
+// for tiles that span the row and with the quotient array: _ok needs a.q != 0
+// and n[2] within the form's tile width, besides the two-step limits; the
+// launch fails, before any kernel, where it is false (callers run the
+// two-step pass or single steps). a.cp is not read.
+int diffusion3d_threestep_num_forms();
+const char* diffusion3d_threestep_form_name(int form);
+bool diffusion3d_threestep_ok(const DiffusionArgs& a);
+void launch_diffusion3d_threestep(const DiffusionArgs& a, hipStream_t stream);
+
 // Fused halo exchange (see fused.hpp): the inner-box update additionally
 // stores its send planes into the receivers' arena regions (`out`, 0 = no
 // receiver at that side) and takes its face halos from its own arena regions

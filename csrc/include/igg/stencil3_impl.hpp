@@ -1,0 +1,318 @@
+// Body and launch of the three-step diffusion pass (scheme: stencil3_kernels.hip).
+// It is the two-step march of stencil2_impl.hpp with one more stage, for the
+// case that kernel's NOZ/QIN specialisation runs: the tile spans the row (no z
+// ring, no edge threads) and the pass reads Q = dtlam/Cp (no division). Every
+// point goes through diffusion_point_q with the operands of the single-step
+// kernel, so the pass leaves bitwise the values of three single steps.
+//
+// As there, every plane-sized register array has three slots, plane j lives in
+// slot (j - first) % 3, and the loop body is unrolled over the three phases.
+// Within a position the work goes row by row - intermediate-1 (p), then
+// intermediate-2 (p-1), then output (p-2) of row r - and the loads of the next
+// position follow the last use of the row they replace (T plane p+2 after
+// stage 1, Q plane p+1 after stage 3), so of each intermediate field and of Q
+// two planes and one row are live, not three planes and a fourth of Q.
+#pragma once
+
+#include "igg/stencil2_impl.hpp"
+
+namespace igg {
+namespace threestep {
+
+using twostep::here;
+using twostep::K2Args;
+using twostep::lane_above;
+using twostep::lane_below;
+using twostep::ldg;
+using twostep::Vec2;
+
+// The value of the lane below / above in the wave, as lane_below / lane_above,
+// but lane 0 / lane 63, which has no such neighbour, keeps `old`: the DPP move
+// leaves its destination alone where the source lane does not exist.
+template <int CTRL>
+__device__ __forceinline__ int lane_shift_keep(int old, int x) {
+  return __builtin_amdgcn_update_dpp(old, x, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float lane_shift_keep(float old, float x) {
+  return __int_as_float(lane_shift_keep<CTRL>(__float_as_int(old), __float_as_int(x)));
+}
+template <int CTRL>
+__device__ __forceinline__ double lane_shift_keep(double old, double x) {
+  return __hiloint2double(lane_shift_keep<CTRL>(__double2hiint(old), __double2hiint(x)),
+                          lane_shift_keep<CTRL>(__double2loint(old), __double2loint(x)));
+}
+
+// A chunk marches four positions before its first output plane; the shortest
+// chunk worth that lead-in.
+constexpr int MIN_CHUNK = 8;
+
+template <typename T, int BY, int RY, int VZ, int BZ>
+__device__ __forceinline__ void body(const K2Args<T>& a) {
+  using V = typename Vec2<T, VZ>::type;
+  constexpr int WS = 64 * VZ;  // points of one wave's row segment
+  constexpr int W = WS * BZ;
+  constexpr int TYE = BY * RY, TYS = TYE - 4;
+  constexpr uint32_t ES = sizeof(T);
+  static_assert(TYE > 4, "a tile writes TYE - 4 rows");
+  static_assert(RY % 2 == 0, "the edge values are loaded in two halves of the wave's rows");
+  // The parts of the two intermediate fields shared between waves, laid out as
+  // in the two-step body: rowsN is [3][BY][2][W] behind one row of padding
+  // (rowsN[RP * slot + lb + k * W], k = 0..3: the last row of the wave below,
+  // this wave's first and last row, the first row of the wave above; k = 0 / 3
+  // of the first / last wave is padding or another slot, read only for ring
+  // rows, whose values are never used), zedgeN is [3][TYE][BZ + 1][2]: per row
+  // the values left ([0]) and right ([1]) of every segment boundary.
+  constexpr int RP = BY * 2 * W;
+  __shared__ __attribute__((aligned(16))) T rows1[3 * RP + 2 * W];
+  __shared__ __attribute__((aligned(16))) T rows2[3 * RP + 2 * W];
+  constexpr int ZR = (BZ + 1) * 2, ZP = TYE * ZR;
+  __shared__ T zedge1[3 * ZP];
+  __shared__ T zedge2[3 * ZP];
+
+  // Indices and in-plane byte offsets are 32-bit (diffusion3d_threestep_ok: a
+  // plane is below 2 GiB); only plane pointers are 64-bit, and wave-uniform.
+  const int b = static_cast<int>(xcd_remap(blockIdx.x, a.nblk));
+  const int nty = static_cast<int>(a.nty);
+  const int ty = b % nty;
+  const int cx = b / nty;
+
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wz = wid % BZ, wy = wid / BZ;
+  const int n0 = static_cast<int>(a.n0), n1 = static_cast<int>(a.n1), n2 = static_cast<int>(a.n2);
+  const uint32_t s1b = n2 * ES, s0b = n1 * s1b;  // row / plane stride in bytes
+  const int zw = wz * WS;                        // segment origin (wave-uniform)
+  const int ye0 = ty * TYS - 1;                  // first ring row of the tile: rows ye0+2 .. ye0+TYE-3 are written
+  const int xs = 1 + cx * static_cast<int>(a.ch);
+  const int xe = min(xs + static_cast<int>(a.ch), n0 - 1);
+  const int p0 = max(xs - 2, 0);  // first march position
+
+  // Lanes past the row alias its last vector (loads stay in bounds, nothing
+  // stored).
+  const int z0 = zw + lane * VZ;
+  const int zc = min(z0, n2 - VZ);
+  const bool zin = z0 < n2;
+  // T's z neighbours of the wave's edge lanes are loaded (lane 0: z-1, lane
+  // 63: z+VZ, clamped to the row: a clamped value only enters a z-boundary
+  // point, which keeps T's value); those of the intermediate fields come from
+  // zedgeN, where i63 selects the lane's side.
+  const bool l63 = lane == 63, ledge = ((lane + 1) & 63) < 2;  // ledge: lane 0 or 63, one compare
+  const int i63 = l63 ? 1 : 0;
+  const int zx = wy * RY * ZR + (wz + i63) * 2 + i63;  // read here, written at zx + 1 - 2 * i63
+  const uint32_t vo = zc * ES;
+  const uint32_t voe = (l63 ? min(zc + VZ, n2 - 1) : max(zc - 1, 0)) * ES;
+  const int lb = wy * 2 * W + wz * WS + lane * VZ;  // the lane's place in the LDS rows
+  const bool vst = zin && (!twostep::zany_of(z0, n2, VZ) || a.halo_z);  // the lane stores whole vectors
+  const bool wvst = __ballot(zin && !vst) == 0;  // ... and so does every lane of the wave that stores at all
+  bool zb[VZ];  // boundary point along z: both intermediate values are T's
+#pragma unroll
+  for (int e = 0; e < VZ; ++e) zb[e] = z0 + e == 0 || z0 + e >= n2 - 1;
+
+  // Rows outside the array alias row 0 / n1-1 (boundary rows: never written).
+  uint32_t rowo[RY];  // wave-uniform row offsets (bytes)
+  bool rbnd[RY], rout[RY];
+#pragma unroll
+  for (int r = 0; r < RY; ++r) {
+    const int yr = ye0 + wy * RY + r;
+    const int lr = wy * RY + r;
+    rowo[r] = min(max(yr, 0), n1 - 1) * s1b;
+    rbnd[r] = yr <= 0 || yr >= n1 - 1;
+    rout[r] = lr >= 2 && lr <= TYE - 3 && yr <= n1 - 2;
+  }
+  const uint32_t rowm = min(max(ye0 + wy * RY - 1, 0), n1 - 1) * s1b;
+  const uint32_t rowp = min(max(ye0 + wy * RY + RY, 0), n1 - 1) * s1b;
+
+  const char* const tb0 = reinterpret_cast<const char*>(a.t);
+  const char* const qb0 = reinterpret_cast<const char*>(a.cp);
+  const T rdx2 = a.rdx2, rdy2 = a.rdy2, rdz2 = a.rdz2;
+
+  // March state, slot = (plane - p0) % 3: tt = T planes p-1, p, p+1; qq = Q
+  // planes p-2 .. p (p+1 row by row into the slot of p-2); i1 = intermediate-1
+  // planes p-2, p-1, p; i2 = intermediate-2 planes p-3, p-2, p-1. ym/yp/ev = T
+  // of plane p around the wave's rows and segment: one slot, reloaded for plane
+  // p+1 behind its use.
+  V tt[3][RY], qq[3][RY], i1[3][RY], i2[3][RY];
+  V ym, yp;
+  T ev[RY];
+  // Plane pointers of the next position's loads, clamped at the last plane
+  // (what is loaded there is unused): T planes p+1 and p+2, Q plane p+1; oo =
+  // byte offset of output plane p-2.
+  const char *t1, *t2, *q1;
+  int64_t oo;
+  {
+    const int64_t pl = s0b;
+    const char* tm = tb0 + max(p0 - 1, 0) * pl;
+    const char* tc = tb0 + p0 * pl;
+    const char* qc = qb0 + p0 * pl;
+    t1 = tc + pl;  // p0 + 1 <= n0 - 1
+    t2 = tb0 + min(p0 + 2, n0 - 1) * pl;
+    q1 = qc + pl;
+    oo = (p0 - 2) * pl;
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+      tt[2][r] = ldg<V>(tm + rowo[r], vo);
+      tt[0][r] = ldg<V>(tc + rowo[r], vo);
+      tt[1][r] = ldg<V>(t1 + rowo[r], vo);
+      qq[0][r] = ldg<V>(qc + rowo[r], vo);
+      ev[r] = T(0);
+      // planes before the chunk: never used by a value that is stored
+      qq[1][r] = qq[2][r] = tt[0][r];
+      i1[1][r] = i1[2][r] = tt[0][r];
+      i2[0][r] = i2[1][r] = i2[2][r] = tt[0][r];
+    }
+    if (ledge) {
+#pragma unroll
+      for (int r = 0; r < RY; ++r) ev[r] = ldg<T>(tc + rowo[r], voe);
+    }
+    ym = ldg<V>(tc + rowm, vo);
+    yp = ldg<V>(tc + rowp, vo);
+  }
+
+  // One stencil update of row r of a plane held in registers `cc` (its x
+  // neighbours xm / xp), whose parts beyond the wave come from `yv` / `yn`
+  // (rows) and `zl` (the edge lanes' z neighbour).
+  auto update = [&](const V& c, const V& xm, const V& xp, const V& yv, const V& yn, T zl, const V& q, bool keep)
+                    __attribute__((always_inline)) {
+    const T prev = lane_shift_keep<0x138>(zl, c[VZ - 1]);  // wave_shr:1, lane 0 keeps zl
+    const T next = lane_shift_keep<0x130>(zl, c[0]);       // wave_shl:1, lane 63 keeps zl
+    V out;
+#pragma unroll
+    for (int e = 0; e < VZ; ++e) {
+      const T zm = e == 0 ? prev : c[e > 0 ? e - 1 : 0];
+      const T zp = e == VZ - 1 ? next : c[e + 1 < VZ ? e + 1 : e];
+      const T v = diffusion_point_q(c[e], xm[e], xp[e], yv[e], yn[e], zm, zp, q[e], rdx2, rdy2, rdz2);
+      out[e] = (keep | zb[e]) ? c[e] : v;  // no short circuit: one select, no branch on the uniform part
+    }
+    return out;
+  };
+
+  // One march position at phase PH = (p - p0) % 3.
+  auto position = [&](auto phase, const int p) __attribute__((always_inline)) {
+    constexpr int PH = decltype(phase)::value;
+    constexpr int SA = (PH + 2) % 3, SB = PH, SN = (PH + 1) % 3;  // slots of planes p-1 (and p-4), p (p-3), p+1 (p-2)
+    const bool pb1 = p <= 0 || p >= n0 - 1;      // boundary plane: the intermediate value is T's
+    const bool pb2 = p - 1 <= 0 || p >= n0;
+    const bool st = p - 2 >= xs;                 // output plane p-2 belongs to the chunk
+    char* const ob = reinterpret_cast<char*>(a.t2) + oo;
+    // the edge lane's place in zedgeN to write, formed here from zx
+    const int zo = static_cast<int>(here(static_cast<uint32_t>(zx))) + 1 - 2 * i63;
+
+#pragma unroll
+    for (int r = 0; r < RY; ++r) {
+      // 1. intermediate-1 plane p, then T plane p+2 into the slot of plane p-1
+      {
+        const V& yv = (r == 0) ? ym : tt[SB][r > 0 ? r - 1 : 0];
+        const V& yn = (r == RY - 1) ? yp : tt[SB][r + 1 < RY ? r + 1 : r];
+        i1[SB][r] = update(tt[SB][r], tt[SA][r], tt[SN][r], yv, yn, ev[r], qq[SB][r], pb1 | rbnd[r]);
+        tt[SA][r] = ldg<V>(t2 + rowo[r], vo);
+        // T of plane p+1 around the wave's rows and segment, behind the use of plane p's
+        if (r == 0) ym = ldg<V>(t1 + rowm, vo);
+        if (r == RY - 1) yp = ldg<V>(t1 + rowp, vo);
+        if (r == RY / 2 - 1 && ledge) {
+#pragma unroll
+          for (int h = 0; h < RY / 2; ++h) ev[h] = ldg<T>(t1 + rowo[h], voe);
+        }
+        if (r == 0) *reinterpret_cast<V*>(&rows1[RP * SB + lb + W]) = i1[SB][r];
+        if (r == RY - 1) *reinterpret_cast<V*>(&rows1[RP * SB + lb + 2 * W]) = i1[SB][r];
+      }
+      // 2. intermediate-2 plane p-1 from intermediate-1 planes p-2, p-1, p
+      {
+        V yv, yn;
+        if (r == 0) yv = *reinterpret_cast<const V*>(&rows1[RP * SA + lb]);
+        else yv = i1[SA][r > 0 ? r - 1 : 0];
+        if (r == RY - 1) yn = *reinterpret_cast<const V*>(&rows1[RP * SA + lb + 3 * W]);
+        else yn = i1[SA][r + 1 < RY ? r + 1 : r];
+        const T zl = zedge1[ZP * SA + r * ZR + zx];  // every lane reads; the edge lanes use it
+        i2[SA][r] = update(i1[SA][r], i1[SN][r], i1[SB][r], yv, yn, zl, qq[SA][r], pb2 | rbnd[r]);
+        if (r == 0) *reinterpret_cast<V*>(&rows2[RP * SA + lb + W]) = i2[SA][r];
+        if (r == RY - 1) *reinterpret_cast<V*>(&rows2[RP * SA + lb + 2 * W]) = i2[SA][r];
+      }
+      // 3. output plane p-2 from intermediate-2 planes p-3, p-2, p-1
+      if (st && rout[r]) {  // wave-uniform
+        V yv, yn;
+        if (r == 0) yv = *reinterpret_cast<const V*>(&rows2[RP * SN + lb]);
+        else yv = i2[SN][r > 0 ? r - 1 : 0];
+        if (r == RY - 1) yn = *reinterpret_cast<const V*>(&rows2[RP * SN + lb + 3 * W]);
+        else yn = i2[SN][r + 1 < RY ? r + 1 : r];
+        const T zl = zedge2[ZP * SN + r * ZR + zx];
+        // z boundary: T's value (written only with halo_z)
+        const V out = update(i2[SN][r], i2[SB][r], i2[SA][r], yv, yn, zl, qq[SN][r], false);
+        T* dst = reinterpret_cast<T*>(ob + rowo[r] + here(vo));
+        if (wvst) {  // wave-uniform: one masked region
+          if (vst) __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
+        } else if (vst) {
+          __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
+        } else if (zin) {
+#pragma unroll
+          for (int e = 0; e < VZ; ++e)
+            if (!zb[e]) dst[e] = out[e];
+        }
+      }
+      // Q plane p+1 into the slot of plane p-2
+      qq[SN][r] = ldg<V>(q1 + rowo[r], vo);
+    }
+    // the edge lanes, one masked region: the other half of the edge values of
+    // plane p+1, and their own values of both new planes for the neighbours
+    if (ledge) {
+#pragma unroll
+      for (int h = RY / 2; h < RY; ++h) ev[h] = ldg<T>(t1 + rowo[h], voe);
+#pragma unroll
+      for (int r = 0; r < RY; ++r) {
+        zedge1[ZP * SB + r * ZR + zo] = l63 ? i1[SB][r][VZ - 1] : i1[SB][r][0];
+        zedge2[ZP * SA + r * ZR + zo] = l63 ? i2[SA][r][VZ - 1] : i2[SA][r][0];
+      }
+    }
+    __syncthreads();
+
+    // the plane pointers of position p+1
+    t1 = t2;
+    if (p + 3 <= n0 - 1) t2 += s0b;
+    if (p + 2 <= n0 - 1) q1 += s0b;
+    oo += s0b;
+  };
+
+  // the last output plane xe-1 is formed at position xe+1
+  for (int p = p0;;) {
+    position(std::integral_constant<int, 0>{}, p);
+    if (p == xe + 1) break;
+    ++p;
+    position(std::integral_constant<int, 1>{}, p);
+    if (p == xe + 1) break;
+    ++p;
+    position(std::integral_constant<int, 2>{}, p);
+    if (p == xe + 1) break;
+    ++p;
+  }
+}
+
+template <typename T, int BY, int RY, int BZ, typename Kern>
+void launch_form(Kern kern, const DiffusionArgs& a, hipStream_t stream) {
+  constexpr int TYS = BY * RY - 4, BLOCK = 64 * BY * BZ;
+  K2Args<T> k;
+  k.t2 = reinterpret_cast<T*>(a.t2);
+  k.t = reinterpret_cast<const T*>(a.t);
+  k.cp = reinterpret_cast<const T*>(a.q);
+  k.n0 = a.n[0]; k.n1 = a.n[1]; k.n2 = a.n[2];
+  k.rdx2 = static_cast<T>(a.rd2[0]);
+  k.rdy2 = static_cast<T>(a.rd2[1]);
+  k.rdz2 = static_cast<T>(a.rd2[2]);
+  k.dtlam = static_cast<T>(a.dt_lam);
+  k.halo_z = a.halo_z ? 1 : 0;
+  k.ntz = 1;
+  k.nty = (k.n1 - 2 + TYS - 1) / TYS;
+  // Equal x chunks so that the grid is about `rounds` residency rounds; a
+  // chunk pays a four-position lead-in, so it is at least MIN_CHUNK planes long.
+  const int64_t len0 = k.n0 - 2, tiles = k.nty;
+  const int64_t target = diffusion3d_target_blocks(reinterpret_cast<const void*>(kern), BLOCK, a.rounds);
+  const int64_t ch_min = std::max<int64_t>(std::min<int64_t>(MIN_CHUNK, len0), (len0 * tiles + target - 1) / target);
+  const int64_t nch = std::max<int64_t>(1, len0 / ch_min);
+  k.ch = (len0 + nch - 1) / nch;
+  k.nblk = tiles * ((len0 + k.ch - 1) / k.ch);
+  if (k.nblk > 0x7fffffffLL) fail("diffusion3d_threestep: grid too large");
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(k.nblk)), dim3(BLOCK), 0, stream, k);
+  IGG_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace threestep
+}  // namespace igg

@@ -19,6 +19,14 @@ GRAPH_STEPS = 10
 # While the two-step pass is on a graph holds passes, and an even number of
 # them hands the ping-pong buffers back in their roles: 20 steps = 10 passes.
 TWOSTEP_GRAPH_STEPS = 20
+# With the deeper (three-step) pass on as well: 100 steps = 32 three-step
+# passes and 2 two-step passes. (A multiple of 6 would hold deep passes only,
+# but the benchmark warms up for its fixed step count rounded up to whole
+# graphs, and its dumped fields are compared between builds: the length
+# divides 200 as TWOSTEP_GRAPH_STEPS does, so that count stays what it was;
+# of the lengths that do, 100 leaves the smallest share, 4 %, to the two-step
+# pass.)
+THREESTEP_GRAPH_STEPS = 100
 
 
 class PingPongModel:
@@ -36,6 +44,11 @@ class PingPongModel:
       whether the model is in that state again (a replay may start);
     * optionally ``_capture_cfg()`` (further settings a graph bakes in) and
       ``_replayed(k)`` (bookkeeping after ``k`` replayed steps);
+    * optionally a deeper pass: ``_deep_pass()``, the launches of one
+      three-step pass (ending like ``_pass()``), and ``_deep_key()``, its
+      setting while ``run``/``capture`` may use it right now and None while
+      not (only ever not None while the two-step pass is on as well). A model
+      without them runs as if the key were always None;
     * ``_fused_handle``: the native fused exchange (None before the first
       ``set_fused(True)``), ``fused``, ``device``;
     * ``_fields``: the checkpointed attributes in file order, ``sync_halo()``
@@ -50,9 +63,16 @@ class PingPongModel:
         self._warm = False  # an eager step ran (halo buffers, plan cache, kernel variant are set up)
         self._graph_two = None  # pass key of the capture, None: single steps
         self._graph_cfg = None  # _capture_cfg() of the capture
+        self._graph_deep = None  # deep key of the capture, None: no deep passes
 
     def _two_step_key(self):
         return self._pass_key() if self._two_step_now() else None
+
+    def _deep_key(self):
+        return None
+
+    def _deep_pass(self) -> None:
+        raise NotImplementedError(f"{type(self).__name__} has no three-step pass")
 
     def _capture_cfg(self):
         return None
@@ -89,7 +109,8 @@ class PingPongModel:
 
     def capture(self, steps: int = None) -> None:
         """Record ``steps`` (even, default GRAPH_STEPS; TWOSTEP_GRAPH_STEPS
-        while the two-step pass is on) time steps in a hipGraph for ``run``.
+        while the two-step pass is on, THREESTEP_GRAPH_STEPS with the deep
+        pass) time steps in a hipGraph for ``run``.
 
         A step is a chain of launches (stencil, pack, RCCL group, unpack per
         dimension; or fused stencil + sync) whose gaps are host launch latency;
@@ -97,7 +118,10 @@ class PingPongModel:
         to launch on MI355X (profiles/r1_fused/), so several steps are captured
         per graph. An even count puts the ping-pong buffers back in their roles
         after every replay; with the two-step pass an even number of PASSES is
-        recorded (``steps // 4 * 2``), closed by ``steps % 4`` single steps.
+        recorded (``steps // 4 * 2``), closed by ``steps % 4`` single steps;
+        with the deep pass ``steps // 6 * 2`` three-step passes come first and
+        that rule holds for the ``steps % 6`` left, so every part swaps the
+        buffers an even number of times.
         The graph holds steady-state steps only: ``capture`` first runs the
         eager steps that needs (the first step sets up halo buffers, plan
         cache and kernel variant; a fused step that primes the arena or
@@ -105,8 +129,11 @@ class PingPongModel:
         """
         name = type(self).__name__
         two = self._two_step_key()
+        deep = self._deep_key()
         if steps is None:
-            steps = TWOSTEP_GRAPH_STEPS if two is not None else GRAPH_STEPS
+            steps = GRAPH_STEPS if two is None else TWOSTEP_GRAPH_STEPS
+            if deep is not None:
+                steps = THREESTEP_GRAPH_STEPS
         steps = int(steps)
         if steps < 2 or steps % 2:
             raise ValueError(f"{name}.capture: steps must be even and >= 2")
@@ -116,10 +143,14 @@ class PingPongModel:
 
         def record():
             singles = steps
+            if deep is not None:
+                singles = steps % 6
+                for _ in range(steps // 6 * 2):
+                    self._deep_pass()
             if two is not None:
-                singles = steps % 4
-                for _ in range(steps // 4 * 2):
+                for _ in range(singles // 4 * 2):
                     self._pass()
+                singles %= 4
             for _ in range(singles):
                 self._step()  # no exit barrier inside the graph: run() drains once
 
@@ -129,6 +160,7 @@ class PingPongModel:
         self.graph = g
         self.graph_steps = steps
         self._graph_two = two
+        self._graph_deep = deep
         self._graph_cfg = self._capture_cfg()
 
     def run(self, nt: int) -> None:
@@ -137,7 +169,9 @@ class PingPongModel:
         none between the steps.
 
         A graph is replayed only if it was captured with the current settings
-        (pass key, ``_capture_cfg``). Its steps have their buffer roles baked
+        (pass key, deep key, ``_capture_cfg``). What no replay covers runs as
+        three-step passes while the deep pass is on (``nt // 3`` of them), then
+        as two-step passes, then as single steps. Its steps have their buffer roles baked
         in and hold no entry barrier, so eager steps realign first: at most
         two. For Acoustic2D the first clears a pending entry barrier and of any
         two consecutive steps one starts from the captured buffer, so it is
@@ -146,7 +180,9 @@ class PingPongModel:
         make the two disagree for good: then the rest runs eagerly."""
         ran = nt > 0
         two = self._two_step_key()
-        if self.graph is not None and self._graph_two == two and self._graph_cfg == self._capture_cfg():
+        deep = self._deep_key()
+        if (self.graph is not None and self._graph_two == two and self._graph_deep == deep
+                and self._graph_cfg == self._capture_cfg()):
             for _ in range(2):
                 if nt == 0 or self._graph_ready():
                     break
@@ -158,6 +194,10 @@ class PingPongModel:
                     self.graph.replay()
                 self._replayed(k * (nt // k))
                 nt %= k
+        if deep is not None:
+            for _ in range(nt // 3):
+                self._deep_pass()
+            nt %= 3
         if two is not None:
             for _ in range(nt // 2):
                 self._pass()
@@ -212,8 +252,8 @@ class PingPongModel:
         """Per-rank checkpoint of the model state (collective; utils.checkpoint).
         Materialises fused-mode halos first (``sync_halo``), so the files hold
         consistent fields. The other ping-pong buffers are saved as they are:
-        the state of one step ago, or of two steps ago if a two-step pass ran
-        last (the next step rewrites them)."""
+        the state of one step ago, or of two / three steps ago if a two-step /
+        three-step pass ran last (the next step rewrites them)."""
         from ..utils.checkpoint import save_checkpoint
 
         self.sync_halo()
@@ -263,8 +303,8 @@ def peer_mesh(ndims: int) -> tuple:
 
 
 def two_step_env(var: str) -> str:
-    """The two-step selection's mode from environment variable ``var``:
-    ``auto`` (default), ``0`` or ``1``."""
+    """The mode of a pass selection (two-step, quotient array, three-step)
+    from environment variable ``var``: ``auto`` (default), ``0`` or ``1``."""
     env = os.environ.get(var, "auto").strip().lower()
     if env not in ("auto", "0", "1"):
         raise ValueError(f"{var} must be auto, 0 or 1, got {env!r}")

@@ -43,8 +43,8 @@ from ..parallel.halo import update_halo_
 from ..utils import placement as _placement
 from ..utils.fields import carve as _carve, ipc_limit, native_buffer  # noqa: F401
 from ..utils.tools import coords_g, nx_g, ny_g, nz_g
-from ._pingpong import (GRAPH_STEPS, TWOSTEP_GRAPH_STEPS, PingPongModel, exchanging_dims,  # noqa: F401
-                        faster_pass, grid_sides, peer_mesh, two_step_env)
+from ._pingpong import (GRAPH_STEPS, THREESTEP_GRAPH_STEPS, TWOSTEP_GRAPH_STEPS, PingPongModel,  # noqa: F401
+                        exchanging_dims, faster_pass, grid_sides, peer_mesh, two_step_env)
 
 # Candidates re-timed by the autotune's ping-pong stage (_choose_variant).
 PINGPONG_FRONT = 4
@@ -95,10 +95,24 @@ class Diffusion3D(PingPongModel):
     (a raw pointer, another process) call ``mark_cp_modified()``. ``auto``
     keeps it where the set-up A/B measures the pass faster with it.
 
+    Three-step pass (``three_step``; IGG_STENCIL_THREESTEP=auto|0|1): where
+    the two-step pass runs with ``Q`` on a grid that exchanges nothing (a rank
+    without neighbours) and a row fits one kernel tile (512 float64 / 1024
+    float32 points), ``run``/``capture`` advance three steps per kernel pass
+    (ops.stencil.diffusion3d_threestep_; bitwise the values of three single
+    steps) and leave what does not fill a pass to the two-step pass and the
+    single step. ``auto`` is considered only while IGG_STENCIL_TWOSTEP is
+    ``auto`` too, and keeps the pass where the set-up A/B measures it faster
+    per step than the selected two-step pass (``three_step_times``); ``1``
+    selects it without timing wherever it can run - the two-step pass with
+    ``Q`` that it rests on included, unless that is forced off. Grids that
+    exchange (a halo three planes deep) are out of its scope.
+
     ``T2`` is the other ping-pong buffer: its boundary planes always equal
     ``T``'s fixed boundary values; its interior is the field of one step ago
-    after a single step and of TWO steps ago after a two-step pass (it is
-    rewritten by whatever runs next either way)."""
+    after a single step, of TWO steps ago after a two-step pass and of THREE
+    after a three-step pass (it is rewritten by whatever runs next either
+    way)."""
 
     _fields = ("T", "T2", "Cp")
 
@@ -127,6 +141,14 @@ class Diffusion3D(PingPongModel):
         self.two_step_form = 0
         self.two_step_rounds = 0
         self.two_step_times = {}
+        # Three-step pass: whether the selection kept it (it stands and falls
+        # with the two-step selection and its variant), its tiling (ops.stencil
+        # THREESTEP_FORMS) and grid rounds, and the A/B's ms per step ("two"
+        # and "d<form>@r<rounds>").
+        self._three_step = False
+        self.three_step_form = 0
+        self.three_step_rounds = 0
+        self.three_step_times = {}
         # The pass's quotient array dt*lam/Cp (None: the pass reads Cp) and
         # what it was built from (Cp's storage and version, dt*lam).
         self.Q = None
@@ -300,6 +322,37 @@ class Diffusion3D(PingPongModel):
     def _pass_key(self):
         return (self.two_step_form, self.two_step_rounds, self.Q is not None)
 
+    @property
+    def three_step(self) -> bool:
+        """The three-step pass is selected, and so is the two-step pass it
+        rests on (``variant`` unchanged since the selection; whether a given
+        ``run`` uses it: ``_deep_key``)."""
+        return self._three_step and self.two_step
+
+    @three_step.setter
+    def three_step(self, flag: bool) -> None:
+        self._three_step = bool(flag)
+
+    def _deep_key(self):
+        """The three-step pass's setting while ``run``/``capture`` may use it
+        right now, else None: selected, the two-step pass eligible and reading
+        ``Q``, nothing exchanged on the grid as it is now, and the kernel has
+        a form for the shape."""
+        if not self.three_step or self.Q is None or not self._two_step_now():
+            return None
+        if exchanging_dims(3) or not stencil.threestep_ok(self.T, self.three_step_form):
+            return None
+        return (self.three_step_form, self.three_step_rounds)
+
+    def _deep_pass(self) -> None:
+        """Three time steps in one pass (callers checked ``_deep_key``): no
+        exchange follows, the grid has none."""
+        stencil.diffusion3d_threestep_(self.T2, self.T, self.Cp, Q=self.Q, lam=self.lam, dt=self.dt, dx=self.dx,
+                                       dy=self.dy, dz=self.dz, form=self.three_step_form,
+                                       rounds=self.three_step_rounds, halo_z=HALO_Z)
+        self._swap()
+        self._warm = True
+
     def _alloc_q(self) -> None:
         """The quotient array, in the fields' kind of memory (not yet built)."""
         meta = torch.empty(self.T.shape, dtype=self.dtype, device="meta")
@@ -340,8 +393,8 @@ class Diffusion3D(PingPongModel):
         (``maxabs_diff_g``): right after a single ``step()`` the largest change
         of the step. It reads owned cells only, none of them a halo plane, so
         it is valid in fused mode without ``sync_halo()``. (After ``run`` the
-        last pass may have been a two-step pass and ``T2`` two steps old: take
-        one ``step()`` first, as ``run_until`` does.)"""
+        last pass may have been a two-step or three-step pass and ``T2`` two
+        or three steps old: take one ``step()`` first, as ``run_until`` does.)"""
         from ..ops.reduce import maxabs_diff_g
 
         return maxabs_diff_g(self.T, self.T2)
@@ -648,16 +701,30 @@ def _select_two_step(m: "Diffusion3D") -> None:
     kernel + update_halo_ and a pass is kernel + ONE update_halo_ for two
     steps; the times are summed over the ranks (every rank must make the same
     choice: one that exchanged every step would mismatch one that exchanges
-    every two), and the timing itself is collective."""
+    every two), and the timing itself is collective.
+
+    The three-step pass (IGG_STENCIL_THREESTEP) is decided here as well, on
+    top of a two-step pass that reads Q on a grid without exchange: 0 off, 1
+    on wherever a form runs the shape, without any timing - the two-step
+    selection is then made as with 1, and with Q, unless either is forced to
+    0 -, auto: considered only while IGG_STENCIL_TWOSTEP is auto too
+    (_select_three_step)."""
     env = two_step_env("IGG_STENCIL_TWOSTEP")
     qenv = two_step_env("IGG_STENCIL_QUOTIENT")
+    denv = two_step_env("IGG_STENCIL_THREESTEP")
     m.two_step = False
+    m.three_step = False
     m.Q = None
     if env == "0" or m.device.type != "cuda" or m.variant is None or not _pass_halo_ok():
         return
     forms = [f for f in stencil.TWOSTEP_FORMS if stencil.twostep_ok(m.T, f)]
     if not forms:
         return
+    deep = [] if denv == "0" or qenv == "0" or exchanging_dims(3) else \
+        [f for f in stencil.THREESTEP_FORMS if stencil.threestep_ok(m.T, f)]
+    auto = env == "auto"
+    if denv == "1" and deep:
+        env = "1"
     if qenv != "0":
         # One more array of the fields' size; "auto" goes on without it where
         # it does not fit, "1" raises.
@@ -680,6 +747,9 @@ def _select_two_step(m: "Diffusion3D") -> None:
     if env == "1":
         m.two_step_form, m.two_step_rounds = forms[0], 0
         m.two_step = True
+        if denv == "1" and deep and m.Q is not None:
+            m.three_step_form, m.three_step_rounds = deep[0], 0
+            m.three_step = True
         return
     rd2 = [1.0 / m.dx ** 2, 1.0 / m.dy ** 2, 1.0 / m.dz ** 2]
     boxes = [(list(b[0]), list(b[1])) for b in m.inner]
@@ -705,6 +775,25 @@ def _select_two_step(m: "Diffusion3D") -> None:
         m.two_step = True
     if best is None or not best[3]:
         m.Q = None  # lost the A/B: the array is freed
+    elif denv == "auto" and auto and deep:
+        _select_three_step(m, rd2, best, deep)
+
+
+def _select_three_step(m: "Diffusion3D", rd2, two, forms) -> None:
+    """The A/B of the three-step pass: the selected two-step candidate ``two``
+    (it reads Q) against every three-step form x GRID_ROUNDS, interleaved, in
+    the time loop's ping-pong shape; the pass is kept only if its time PER
+    STEP is below the two-step pass's. The ms per step go into
+    ``m.three_step_times`` ("two" and "d<form>@r<rounds>"). No exchange and
+    one rank's choice: the pass is considered only on a grid without any."""
+    cands = [(f, r, HALO_Z) for f in forms for r in stencil.GRID_ROUNDS]
+    t2, t = stencil.time_threestep_pingpong(m.T2, m.T, m.Cp, rd2, m.dt * m.lam, two[:3], cands, m.Q)
+    m.three_step_times = {"two": round(t2, 5)}
+    m.three_step_times.update({f"d{c[0]}@r{c[1]}": round(x, 5) for c, x in t.items()})
+    best = min(t, key=t.get)
+    if t[best] < t2:
+        m.three_step_form, m.three_step_rounds = int(best[0]), int(best[1])
+        m.three_step = True
 
 
 def _hw_queues() -> int | None:

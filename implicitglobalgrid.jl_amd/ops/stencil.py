@@ -287,6 +287,74 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
     return med.pop(None), med
 
 
+# Tilings of the three-step pass (csrc/kernels/stencil3_kernels.hip).
+THREESTEP_FORMS = tuple(range(len(native.diffusion3d_threestep_forms())))
+
+
+def threestep_ok(T, form: int = 0) -> bool:
+    """Whether three-step form ``form`` can run on ``T``: what ``twostep_ok``
+    asks, and rows no longer than the form's tile (512 float64 / 1024 float32
+    points for form 0). The pass also needs the quotient array."""
+    if not (T.is_cuda and T.dim() == 3 and T.is_contiguous() and T.dtype in (torch.float32, torch.float64)):
+        return False
+    return bool(native.diffusion3d_threestep_ok(list(T.shape), T.element_size(), int(form)))
+
+
+def diffusion3d_threestep_(T2, T, Cp, *, Q, lam: float, dt: float, dx: float, dy: float, dz: float,
+                           form: int = 0, rounds: int = 0, halo_z: bool = False, stream: int | None = None) -> None:
+    """Three diffusion updates in one pass over memory: afterwards ``T2``
+    holds, bitwise, what three ``diffusion3d_`` calls ``T -> tmp1 -> tmp2 ->
+    T2`` on the whole interior leave, where both ``tmp``'s boundary planes
+    equal ``T``'s. The pass reads ``T`` and ``Q``, the array ``quotient_`` left
+    for this ``Cp`` and ``dt * lam`` (required: it has no dividing form);
+    ``Cp`` is only checked against. ``T2``'s boundary planes are not written
+    (``halo_z`` as in ``diffusion3d_``). GPU only; raises ``IGGError``, before
+    anything is written, where ``threestep_ok`` is false or ``Q`` is missing
+    (callers then run the two-step pass or single steps)."""
+    _check(T2, T, Cp)
+    if not T.is_cuda:
+        raise IGGError("diffusion3d_threestep: GPU tensors only (there is no host three-step kernel)")
+    if Q is None:
+        raise IGGError("diffusion3d_threestep: the pass reads the quotient array Q (quotient_)")
+    if not threestep_ok(T, form):
+        raise IGGError(f"diffusion3d_threestep: form {form} cannot run shape {tuple(T.shape)} {T.dtype}")
+    _check_q(Q, Cp)
+    if Q.data_ptr() in (T.data_ptr(), T2.data_ptr()):
+        raise IGGError("diffusion3d_threestep: Q aliases a field")
+    rd2 = [1.0 / (dx * dx), 1.0 / (dy * dy), 1.0 / (dz * dz)]
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    native.diffusion3d_threestep(T2.data_ptr(), T.data_ptr(), Q.data_ptr(), list(T.shape), rd2, dt * lam,
+                                 T.element_size(), int(form), s, int(rounds), bool(halo_z))
+
+
+def time_threestep_pingpong(T2, T, Cp, rd2, dtlam, two, candidates, Q, steps: int = 24, rounds: int = 5) -> tuple:
+    """Median ms PER STEP of the two-step candidate ``two`` (form, rounds,
+    halo_z; reading ``Q``) and of each three-step candidate (form, rounds,
+    halo_z), interleaved, in the time loop's ping-pong shape on the model's own
+    two buffers (``steps`` a multiple of 12: an even number of passes of
+    either depth). No exchange: the three-step pass runs only on a grid that
+    has none. T is saved and restored; T2's interior is scribbled. Returns
+    (two-step ms, {candidate: ms})."""
+    n, es, s = list(T.shape), T.element_size(), torch.cuda.current_stream().cuda_stream
+
+    def run(c, k):
+        for j in range(k // 2 if c is None else k // 3):
+            dst, src = (T2, T) if j % 2 == 0 else (T, T2)
+            if c is None:
+                f, gr, hz = two[:3]
+                native.diffusion3d_twostep(dst.data_ptr(), src.data_ptr(), Cp.data_ptr(), n, rd2, dtlam, es, f, s, gr,
+                                           hz, Q.data_ptr())
+            else:
+                f, gr, hz = c[:3]
+                native.diffusion3d_threestep(dst.data_ptr(), src.data_ptr(), Q.data_ptr(), n, rd2, dtlam, es, f, s, gr,
+                                             hz)
+
+    order = [None] + list(candidates)  # None: the two-step candidate
+    with _kept(T):
+        med = dict(zip(order, interleaved_medians(order, run, steps, rounds, warm=12)))
+    return med.pop(None), med
+
+
 def _acoustic_shapes_ok(P, Vx, Vy) -> bool:
     if P.dim() != 2:
         return False

@@ -27,6 +27,11 @@ two-steps-per-pass kernel on a rank without neighbours),
 array ``dt*lam/Cp`` the model keeps - one more array of the fields' size -
 instead of dividing; ``auto`` keeps it where the set-up timing finds the pass
 faster with it, and means on where ``IGG_STENCIL_TWOSTEP=1`` skips the timing),
+``IGG_STENCIL_THREESTEP`` (``auto`` | ``0`` | ``1``: three steps per pass on top
+of that pass with the quotient array, rows within one kernel tile, a grid that
+exchanges nothing; ``auto`` times it against the two-step pass and is
+considered only while ``IGG_STENCIL_TWOSTEP`` is ``auto``; ``1`` selects it
+without timing wherever it can run, the two-step pass and the array included),
 ``IGG_ACOUSTIC_TWOSTEP`` (the same for the acoustic model), ``IGG_DEBUG_SYNC`` (synchronise after every halo update), ``IGG_QUIET``.
 """
 from __future__ import annotations
