@@ -201,7 +201,7 @@ def test_plan_paths_and_index_widths():
     assert native.select_plan((3, 5, 9), (50, 10, 1), (90, 18, 2))["path"] == "element"
     assert native.select_plan((3, 5, 9), (1, 3, 15), (45, 9, 1))["path"] == "element"
     assert native.select_plan((3, 0, 9), (50, 10, 1), (45, 9, 1))["blocks"] == 0
-    # 64-bit offsets: asserted here only - running them would need a 16 GiB field
+    # 64-bit offsets: the plan here; the 64-bit kernel runs in tests/test_gpu_large_offsets.py (a 17 GB field)
     big = native.select_plan((1300, 1300, 1300), (1300 * 1300, 1300, 1), (1300 * 1300, 1300, 1))
     assert big["index_bits"] == 64 and big["path"] == "rows" and big["blocks"] == native.SELECT_MAX_BLOCKS
     assert native.select_plan((2, 2, 2), (1 << 31, 4, 2), (4, 2, 1))["index_bits"] == 64    # the source span alone
