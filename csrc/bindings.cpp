@@ -45,6 +45,22 @@ using namespace igg;
 
 namespace {
 
+// A job of the converting lattice copies as Python passes it: (src, dst, counts, src strides, dst strides).
+using SelectTuple =
+    std::tuple<uintptr_t, uintptr_t, std::array<int64_t, 3>, std::array<int64_t, 3>, std::array<int64_t, 3>>;
+
+std::vector<SelectDesc> select_descs(const std::vector<SelectTuple>& jobs) {
+  std::vector<SelectDesc> v;
+  v.reserve(jobs.size());
+  for (const auto& t : jobs) {
+    SelectDesc j;
+    j.src = std::get<0>(t), j.dst = std::get<1>(t);
+    for (int d = 0; d < 3; ++d) j.c[d] = std::get<2>(t)[d], j.S[d] = std::get<3>(t)[d], j.T[d] = std::get<4>(t)[d];
+    v.push_back(j);
+  }
+  return v;
+}
+
 // DLPack (v0.8 ABI, the layout torch.utils.dlpack consumes): a native device
 // allocation of a given memory kind handed to torch as a 1-D uint8 tensor
 // whose deleter frees it. Lets a model keep its fields in fine-grained memory
@@ -626,23 +642,15 @@ PYBIND11_MODULE(_igg_native, m) {
         "What select_convert does with one job (counts and strides in elements, outer .. inner): path (rows / "
         "element), index_bits (32 / 64), elements, rows, spans and blocks (0: empty, skipped).");
   m.def("select_convert",
-        [](const std::vector<std::tuple<uintptr_t, uintptr_t, std::array<int64_t, 3>, std::array<int64_t, 3>,
-                                        std::array<int64_t, 3>>>& jobs,
-           uintptr_t stream) {
-          std::vector<SelectDesc> v;
-          v.reserve(jobs.size());
-          for (const auto& t : jobs) {
-            SelectDesc j;
-            j.src = std::get<0>(t), j.dst = std::get<1>(t);
-            for (int d = 0; d < 3; ++d)
-              j.c[d] = std::get<2>(t)[d], j.S[d] = std::get<3>(t)[d], j.T[d] = std::get<4>(t)[d];
-            v.push_back(j);
-          }
-          select_convert(v, as_stream(stream));
-        },
+        [](const std::vector<SelectTuple>& jobs, uintptr_t stream) { select_convert(select_descs(jobs), as_stream(stream)); },
         py::arg("jobs"), py::arg("stream") = 0,
         "dst[i0*T0 + i1*T1 + i2*T2] (f32, device) = float(src[i0*S0 + i1*S1 + i2*S2]) (f64, device), i_d < c_d, for "
         "every job (src, dst, counts, src strides, dst strides); strides in elements.");
+  m.def("select_widen",
+        [](const std::vector<SelectTuple>& jobs, uintptr_t stream) { select_widen(select_descs(jobs), as_stream(stream)); },
+        py::arg("jobs"), py::arg("stream") = 0,
+        "dst[i0*T0 + i1*T1 + i2*T2] (f64, device) = double(src[i0*S0 + i1*S1 + i2*S2]) (f32, device), i_d < c_d, for "
+        "every job (src, dst, counts, src strides, dst strides); strides in elements. The plan is select_plan's.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

@@ -7,6 +7,11 @@
 // travel), the root writes its own block straight into its box of the global
 // array (dst strides of that array).
 //
+// scatter_g needs the mirror image at the receiver: select_widen reads an f32
+// lattice (a compact staging buffer, or a box of a float32 global array) and
+// writes static_cast<double> of it into an f64 field - exact, and again only
+// half the bytes travelled. Same jobs, same batches, same plan.
+//
 // One launch takes up to SELECT_MAX_JOBS jobs, each with its own block range
 // (as ReduceBatch). The path of a job comes from a host plan (plan_select),
 // shared by the launcher and the tests (native.select_plan).
@@ -47,18 +52,25 @@ struct SelectPlan {
 // not be negative.
 SelectPlan plan_select(const int64_t c[3], const int64_t S[3], const int64_t T[3]);
 
-struct SelectJob {
-  const double* src;  // the first selected element
-  float* dst;
+template <typename In, typename Out>
+struct SelectJobT {
+  const In* src;  // the first selected element
+  Out* dst;
   int64_t c[3], S[3], T[3];
   int rows;  // SelectPath::rows
 };
 
-struct SelectBatch {
+template <typename Job>
+struct SelectBatchT {
   int n;
   uint32_t block_start[SELECT_MAX_JOBS + 1];
-  SelectJob job[SELECT_MAX_JOBS];
+  Job job[SELECT_MAX_JOBS];
 };
+
+using SelectJob = SelectJobT<double, float>;  // select_convert: f64 in, f32 out
+using SelectBatch = SelectBatchT<SelectJob>;
+using WidenJob = SelectJobT<float, double>;  // select_widen: f32 in, f64 out
+using WidenBatch = SelectBatchT<WidenJob>;
 
 struct SelectDesc {
   uintptr_t src = 0, dst = 0;
@@ -70,7 +82,14 @@ struct SelectDesc {
 // synchronises.
 void select_convert(const std::vector<SelectDesc>& jobs, hipStream_t stream);
 
+// The same for f32 in, f64 out (rows path: 16-B f64x2 stores aligned on the
+// destination, at most one head and three tail elements stored singly, the
+// lanes of a wave exchanging their floats so that each store instruction is
+// contiguous; the source needs only its element's alignment).
+void select_widen(const std::vector<SelectDesc>& jobs, hipStream_t stream);
+
 // select_kernels.hip
 void launch_select_convert(const SelectBatch& batch, bool wide, hipStream_t stream);
+void launch_select_widen(const WidenBatch& batch, bool wide, hipStream_t stream);
 
 }  // namespace igg

@@ -17,7 +17,9 @@ which every global cell counts once (``reduce_g``, ``sum_g``, ``norm_g``,
 over some axes and keeps the others (profiles, column maxima), and
 ``gather_g``, which assembles the true global field - whole, a box of it or
 every n-th cell - from the owned cells (``indices_g``, ``selection_shape_g``;
-parallel/gather_g.py).
+parallel/gather_g.py), and its inverse ``scatter_g``, which fills the local
+fields of all ranks from a global array on a root (``scatter_pieces``;
+parallel/scatter_g.py).
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -33,6 +35,7 @@ from .parallel.halo import update_halo, update_halo_  # noqa: F401
 from .parallel.transport_select import select_transport  # noqa: F401
 from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
 from .parallel.gather_g import gather_g, indices_g, selection_shape_g  # noqa: F401
+from .parallel.scatter_g import scatter_g, scatter_pieces  # noqa: F401
 from .utils.tools import coords_g, nx_g, ny_g, nz_g, tic, toc, x_g, y_g, z_g  # noqa: F401
 from .utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .ops.reduce import (  # noqa: F401
@@ -59,4 +62,5 @@ __all__ = [
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
     "norm_g", "norm_diff_g", "mean_g", "project_g", "gather_g", "indices_g", "selection_shape_g",
+    "scatter_g", "scatter_pieces",
 ]

@@ -91,26 +91,27 @@ def _segments(n: int, o: int, D: int, per: int, c: int, m: int) -> list:
     return [(g0, ng, a), (0, g0 + (b - a) - ng, a + (ng - g0))]
 
 
-def normalize_selection(nxyz, overlaps, dims, periods, shape, box=None, step=1) -> list:
+def normalize_selection(nxyz, overlaps, dims, periods, shape, box=None, step=1, who="gather_g") -> list:
     """``[(lo, hi, step)]`` per dimension of ``shape`` from ``box`` (per
     dimension ``None``, an int ``g`` meaning ``[g, g + 1)``, or ``(lo, hi)``)
     and ``step`` (an int or one per dimension); raises ``IGGError`` on a wrong
-    length, ``step < 1`` or an empty or out-of-range box."""
+    length, ``step < 1`` or an empty or out-of-range box, in the name of
+    ``who``."""
     nd = len(shape)
     if box is None:
         box = (None,) * nd
     if not isinstance(box, (tuple, list)) or len(box) != nd:
-        raise IGGError(f"gather_g: `box` needs one entry per dimension of the field ({nd}).")
+        raise IGGError(f"{who}: `box` needs one entry per dimension of the field ({nd}).")
     if not isinstance(step, (tuple, list)):
         step = (step,) * nd
     if len(step) != nd:
-        raise IGGError(f"gather_g: `step` needs one entry per dimension of the field ({nd}).")
+        raise IGGError(f"{who}: `step` needs one entry per dimension of the field ({nd}).")
     sel = []
     for d in range(nd):
         ext = _extent(int(nxyz[d]), int(overlaps[d]), int(dims[d]), int(periods[d]), int(shape[d]))
         s = step[d]
         if not isinstance(s, int) or isinstance(s, bool) or s < 1:
-            raise IGGError(f"gather_g: `step` must be an integer >= 1 (got {s!r} in dimension {d}).")
+            raise IGGError(f"{who}: `step` must be an integer >= 1 (got {s!r} in dimension {d}).")
         b = box[d]
         if b is None:
             lo, hi = 0, ext
@@ -120,9 +121,9 @@ def normalize_selection(nxyz, overlaps, dims, periods, shape, box=None, step=1) 
             try:
                 lo, hi = (int(v) for v in b)
             except (TypeError, ValueError):
-                raise IGGError(f"gather_g: `box` entry {b!r} is not None, an int or a (lo, hi) pair.") from None
+                raise IGGError(f"{who}: `box` entry {b!r} is not None, an int or a (lo, hi) pair.") from None
         if lo < 0 or hi > ext or lo >= hi:
-            raise IGGError(f"gather_g: box [{lo}, {hi}) of dimension {d} is empty or outside of [0, {ext}).")
+            raise IGGError(f"{who}: box [{lo}, {hi}) of dimension {d} is empty or outside of [0, {ext}).")
         sel.append((lo, hi, s))
     return sel
 

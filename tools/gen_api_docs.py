@@ -21,6 +21,7 @@ SECTIONS = [
     ("Halo update", "igg", ["update_halo_", "select_transport"]),
     ("Gather", "igg", ["gather_", "gather_async_"]),
     ("The global field: whole, sliced or coarsened", "igg", ["gather_g", "selection_shape_g", "indices_g"]),
+    ("A global array into the fields", "igg", ["scatter_g", "scatter_pieces"]),
     ("Global sizes and coordinates, timing", "igg",
      ["nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "coords_g", "tic", "toc"]),
     ("Global reductions", "igg",
