@@ -225,6 +225,32 @@ struct FieldSet {
   std::vector<Field> f;
 };
 
+AccumType accum_type(const std::string& dtype) {
+  static const std::pair<const char*, AccumType> names[] = {
+      {"float32", AccumType::F32}, {"float64", AccumType::F64}, {"int8", AccumType::I8},
+      {"int16", AccumType::I16},   {"int32", AccumType::I32},   {"int64", AccumType::I64},
+      {"uint8", AccumType::U8},    {"float16", AccumType::F16}, {"bfloat16", AccumType::BF16},
+      {"complex64", AccumType::C64}, {"complex128", AccumType::C128}};
+  for (const auto& n : names)
+    if (dtype == n.first) return n.second;
+  fail("accumulate: unsupported element type '", dtype, "'");
+}
+
+std::vector<Accum3D> to_accums(const std::vector<std::array<int64_t, 9>>& boxes,
+                               const std::vector<std::pair<uintptr_t, uintptr_t>>& ptrs,
+                               const std::vector<std::string>& ops) {
+  if (boxes.size() != ptrs.size() || boxes.size() != ops.size())
+    fail("accum3d: one (src, dst) pair and one operation per box");
+  std::vector<Accum3D> v;
+  for (size_t k = 0; k < boxes.size(); ++k) {
+    const auto& b = boxes[k];
+    v.push_back({{reinterpret_cast<const char*>(ptrs[k].first), reinterpret_cast<char*>(ptrs[k].second), b[0], b[1],
+                  b[2], b[3], b[4], b[5], b[6], b[7], b[8]},
+                 accum_op_from_name(ops[k].c_str())});
+  }
+  return v;
+}
+
 std::vector<Box> to_boxes(const std::vector<std::pair<Int3, Int3>>& bs) {
   std::vector<Box> out;
   for (const auto& b : bs) {
@@ -504,6 +530,42 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("box"), py::arg("ptrs"), py::arg("elem_bytes"),
         "What launch_copy3d does with one box: the normalised box (extents, src strides, dst strides), path "
         "(flat / gather / chunk), vec_bytes (0, 4, 8 or 16) and blocks.");
+
+  // --- accumulation (the transposed halo exchange's kernels)
+  m.def("accum3d",
+        [](const std::vector<std::array<int64_t, 9>>& boxes, const std::vector<std::pair<uintptr_t, uintptr_t>>& ptrs,
+           const std::vector<std::string>& ops, const std::string& dtype, uintptr_t stream) {
+          launch_accum3d(to_accums(boxes, ptrs, ops), accum_type(dtype), as_stream(stream));
+        },
+        py::arg("boxes"), py::arg("ptrs"), py::arg("ops"), py::arg("dtype"), py::arg("stream") = 0,
+        "Batched strided accumulation on the GPU: boxes and (src, dst) pointers as for copy3d, one operation "
+        "per box ('add': dst += src; 'take': dst = src, src = 0; 'add_take': both; 'zero': dst = 0); dtype "
+        "'float32' or 'float64'. Descriptors of one call must not share cells.");
+  m.def("host_accum3d",
+        [](const std::vector<std::array<int64_t, 9>>& boxes, const std::vector<std::pair<uintptr_t, uintptr_t>>& ptrs,
+           const std::vector<std::string>& ops, const std::string& dtype) {
+          host_accum3d(to_accums(boxes, ptrs, ops), accum_type(dtype));
+        },
+        py::arg("boxes"), py::arg("ptrs"), py::arg("ops"), py::arg("dtype"),
+        "accum3d on host memory, one descriptor after the other; every torch dtype that adds, bool excepted.");
+  m.def("accum3d_plan",
+        [](const std::array<int64_t, 9>& b, const std::pair<uintptr_t, uintptr_t>& ptrs, const std::string& dtype) {
+          const CopyPlan3 p = plan_accum3d(
+              {reinterpret_cast<const char*>(ptrs.first), reinterpret_cast<char*>(ptrs.second), b[0], b[1], b[2],
+               b[3], b[4], b[5], b[6], b[7], b[8]},
+              accum_elem_bytes(accum_type(dtype)), g_copy_gather);
+          py::dict d;
+          d["box"] = py::make_tuple(p.box.n_outer, p.box.n_mid, p.box.n_inner, p.box.src_so, p.box.src_sm,
+                                    p.box.src_si, p.box.dst_so, p.box.dst_sm, p.box.dst_si);
+          d["path"] = copy_path_name(p.path);
+          d["vec_bytes"] = p.vec_bytes;
+          d["blocks"] = p.blocks;
+          return d;
+        },
+        py::arg("box"), py::arg("ptrs"), py::arg("dtype"),
+        "What accum3d does with one box: the normalised box, path (flat / gather / chunk), vec_bytes (gather: "
+        "the row as one access of 4, 8 or 16 bytes; chunk: 16 where both sides are aligned; else 0) and blocks.");
+  m.attr("MAX_BATCH") = MAX_BATCH;
 
   // --- reductions (ops/reduce.py)
   m.attr("REDUCE_MAX_BLOCKS") = REDUCE_MAX_BLOCKS;
@@ -843,6 +905,12 @@ PYBIND11_MODULE(_igg_native, m) {
       .def("exchange_set",
            [](HaloEngine& e, const FieldSet& fs, uintptr_t s, int mode) { e.exchange(fs.f, as_stream(s), mode); },
            py::arg("fields"), py::arg("stream"), py::arg("mode") = -1)
+      .def("accumulate_set",
+           [](HaloEngine& e, const FieldSet& fs, const std::string& dtype, uintptr_t s,
+              std::shared_ptr<Transport> dev_transport) {
+             e.accumulate(fs.f, accum_type(dtype), as_stream(s), dev_transport);
+           },
+           py::arg("fields"), py::arg("dtype"), py::arg("stream"), py::arg("dev_transport") = nullptr)
       .def("exchange_dim",
            [](HaloEngine& e, const std::vector<FieldTuple>& fs, int dim, uintptr_t s) {
              e.exchange_dim(to_fields(fs), dim, as_stream(s));

@@ -1,6 +1,10 @@
 // Host-side plan of the batched copy kernels (igg/copy_plan.hpp).
 #include "igg/copy_plan.hpp"
 
+#include <cstring>
+
+#include "igg/accum.hpp"
+
 namespace igg {
 
 Copy3D normalized(Copy3D c) {
@@ -72,6 +76,47 @@ CopyPlan3 plan_copy3d(const Copy3D& in, int elem_bytes, const ParityShift& par, 
   p.blocks = is_flat     ? (total + COPY_BLOCK - 1) / COPY_BLOCK
              : is_gather ? ((c.n_mid + 63) / 64) * ((c.n_outer + 4 * COPY_GROWS - 1) / (4 * COPY_GROWS))
                          : c.n_outer * c.n_mid * ((c.n_inner + COPY_CHUNK - 1) / COPY_CHUNK);
+  return p;
+}
+
+// ---------------------------------------------------------------- accumulation
+
+const char* accum_op_name(AccumOp op) {
+  switch (op) {
+    case AccumOp::Add: return "add";
+    case AccumOp::Take: return "take";
+    case AccumOp::AddTake: return "add_take";
+    case AccumOp::Zero: return "zero";
+  }
+  return "?";
+}
+
+AccumOp accum_op_from_name(const char* name) {
+  for (AccumOp op : {AccumOp::Add, AccumOp::Take, AccumOp::AddTake, AccumOp::Zero})
+    if (std::strcmp(name, accum_op_name(op)) == 0) return op;
+  fail("accum3d: unknown operation '", name, "' (add, take, add_take or zero)");
+}
+
+int accum_elem_bytes(AccumType t) {
+  switch (t) {
+    case AccumType::I8: case AccumType::U8: return 1;
+    case AccumType::I16: case AccumType::F16: case AccumType::BF16: return 2;
+    case AccumType::F32: case AccumType::I32: return 4;
+    case AccumType::F64: case AccumType::I64: case AccumType::C64: return 8;
+    case AccumType::C128: return 16;
+  }
+  fail("accum3d: unknown element type ", static_cast<int>(t));
+}
+
+CopyPlan3 plan_accum3d(const Copy3D& in, int elem_bytes, bool gather) {
+  CopyPlan3 p = plan_copy3d(in, elem_bytes, ParityShift{}, gather);
+  if (p.blocks <= 0 || p.path != CopyPath::chunk) return p;
+  const Copy3D& c = p.box;
+  auto ok = [&](const char* q, int64_t sm, int64_t so) {
+    return reinterpret_cast<uintptr_t>(q) % 16 == 0 && (sm * elem_bytes) % 16 == 0 && (so * elem_bytes) % 16 == 0;
+  };
+  if (c.src_si == 1 && c.dst_si == 1 && ok(c.src, c.src_sm, c.src_so) && ok(c.dst, c.dst_sm, c.dst_so))
+    p.vec_bytes = 16;
   return p;
 }
 

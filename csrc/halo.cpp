@@ -718,3 +718,148 @@ void HaloEngine::exchange_onephase(const std::vector<Field>& fields, bool device
 }
 
 }  // namespace igg
+
+// ------------------------------------------------- transposed exchange
+//
+// H = H_z H_y H_x (the sequential schedule above), so its transpose runs the
+// dimensions backwards: H^T = H_x^T H_y^T H_z^T. H_d overwrites each halo slab
+// that has a neighbour with that neighbour's send slab and leaves the rest
+// alone; as a matrix, row "halo cell" has its single 1 in column "neighbour's
+// send cell". Transposed: a halo cell's value moves to the neighbour's send
+// cell (added to what is there) and the halo cell, whose column in H_d is
+// empty, becomes zero.
+
+namespace igg {
+
+void HaloEngine::accumulate(const std::vector<Field>& fields, AccumType type, hipStream_t stream,
+                            const std::shared_ptr<Transport>& dev_transport) {
+  if (fields.empty()) return;
+  TraceRange tr("igg.accumulate_halo");
+  const bool device = fields[0].device;
+  for (const Field& f : fields) {
+    if (f.elem_bytes != accum_elem_bytes(type)) fail("accumulate_halo: element size and type disagree");
+    for (int d = 0; d < NDIMS; ++d) {
+      const bool nb = grid_.neighbors[0][d] != PROC_NULL || grid_.neighbors[1][d] != PROC_NULL;
+      if (nb && ol(grid_, d, f) >= 2 && f.size[d] < ol(grid_, d, f) + grid_.halowidths[d])
+        fail("Incoherent arguments: size(A,dim)<ol(A,dim)+halowidths[dim]; a send range would overlap a halo.");
+    }
+  }
+  bool capturing = false;
+  if (device) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    IGG_HIP_CHECK(hipStreamIsCapturing(stream, &cs));
+    capturing = cs != hipStreamCaptureStatusNone;
+  }
+  struct Freeze {
+    BufferPool& p;
+    Freeze(BufferPool& q, bool on) : p(q) { p.set_frozen(on); }
+    ~Freeze() { p.set_frozen(false); }
+  } freeze(pool_, capturing);
+  pool_.ensure(fields, device);
+  if (device) {
+    // (the pool is shared with the exchange: the same ordering against the previous user)
+    if (!done_) IGG_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+    if (!capturing && have_event_ && last_stream_ != stream) IGG_HIP_CHECK(hipStreamWaitEvent(stream, done_, 0));
+  }
+  const std::shared_ptr<Transport>& transport = device ? dev_transport : host_transport_;
+  for (int dim = NDIMS - 1; dim >= 0; --dim) accumulate_dim(fields, type, dim, device, stream, transport);
+  if (device && !capturing) {
+    IGG_HIP_CHECK(hipEventRecord(done_, stream));
+    have_event_ = true;
+    last_stream_ = stream;
+  }
+}
+
+void HaloEngine::accumulate_dim(const std::vector<Field>& fields, AccumType type, int dim, bool device,
+                                hipStream_t stream, const std::shared_ptr<Transport>& transport) {
+  const GridInfo& g = grid_;
+  const int64_t left = g.neighbors[0][dim], right = g.neighbors[1][dim];
+  const bool has[2] = {left != PROC_NULL, right != PROC_NULL};
+  if (!has[0] && !has[1]) return;
+  const int64_t w = g.halowidths[dim];
+  auto run = [&](const std::vector<Accum3D>& ops) {
+    if (ops.empty()) return;
+    if (device) launch_accum3d(ops, type, stream);
+    else host_accum3d(ops, type);
+  };
+  // The two send slabs of a field share planes (size < 2*ol): the right-hand
+  // message is added by a second launch, after the left-hand one.
+  auto shared_planes = [&](const Field& f) {
+    return has[0] && has[1] && send_index(g, 1, dim, f) < send_index(g, 0, dim, f) + w;
+  };
+  static const char* const kSelf[3] = {"igg.adj.self.x", "igg.adj.self.y", "igg.adj.self.z"};
+  static const char* const kTake[3] = {"igg.adj.take.x", "igg.adj.take.y", "igg.adj.take.z"};
+  static const char* const kComm[3] = {"igg.adj.transport.x", "igg.adj.transport.y", "igg.adj.transport.z"};
+  static const char* const kAdd[3] = {"igg.adj.add.x", "igg.adj.add.y", "igg.adj.add.z"};
+
+  if (left == g.me && right == g.me) {
+    // The message "from the left neighbour" is this rank's own right halo slab.
+    TraceRange r(kSelf[dim]);
+    std::vector<Accum3D> first, second;
+    for (const Field& f : fields) {
+      if (ol(g, dim, f) < 2) continue;
+      for (int s = 0; s < NNEIGHBORS; ++s)
+        (s == 1 && shared_planes(f) ? second : first)
+            .push_back({move_copy(slab(f, dim, recv_index(g, 1 - s, dim, f), w),
+                                  slab(f, dim, send_index(g, s, dim, f), w)),
+                        AccumOp::AddTake});
+    }
+    run(first);
+    run(second);
+    debug_phase(stream, device, kSelf[dim]);
+    return;
+  }
+  if (left == g.me || right == g.me)
+    fail("Incoherent neighbors in dimension ", dim + 1, ": either all neighbors must equal to me, or none.");
+  if (!transport)
+    fail("accumulate_halo: no transport available to reach neighbours in dimension ", dim + 1,
+         " (multi-process exchange needs an initialised communicator).");
+  if (device ? !transport->device_capable() : !transport->host_capable())
+    fail("accumulate_halo: transport '", transport->name(), "' cannot move ", device ? "GPU" : "host", " memory.");
+
+  std::vector<Accum3D> take, first, second;
+  std::vector<P2POp> recvs, sends;
+  // Message order and tags as in exchange_dim_impl: receives right then left,
+  // sends left then right; the receiver files a message under its opposite side.
+  for (int s = NNEIGHBORS - 1; s >= 0; --s) {
+    if (!has[s]) continue;
+    for (size_t i = 0; i < fields.size(); ++i) {
+      const Field& f = fields[i];
+      if (ol(g, dim, f) < 2) continue;
+      const Face sf = slab(f, dim, send_index(g, s, dim, f), w);
+      recvs.push_back({pool_.recv(i, s, device), sf.bytes, static_cast<int>(g.neighbors[s][dim]),
+                       static_cast<int>(i * 2 + s)});
+    }
+  }
+  for (int s = 0; s < NNEIGHBORS; ++s) {
+    if (!has[s]) continue;
+    for (size_t i = 0; i < fields.size(); ++i) {
+      const Field& f = fields[i];
+      if (ol(g, dim, f) < 2) continue;
+      const Face hf = slab(f, dim, recv_index(g, s, dim, f), w);
+      char* ptr = hf.contiguous ? hf.base : pool_.send(i, s, device);
+      if (hf.contiguous) first.push_back({move_copy(hf, hf), AccumOp::Zero});
+      else take.push_back({pack_copy(hf, ptr), AccumOp::Take});
+      sends.push_back({ptr, hf.bytes, static_cast<int>(g.neighbors[s][dim]), static_cast<int>(i * 2 + (1 - s))});
+      const Face sf = slab(f, dim, send_index(g, s, dim, f), w);
+      (s == 1 && shared_planes(f) ? second : first)
+          .push_back({unpack_copy(pool_.recv(i, s, device), sf), AccumOp::Add});
+    }
+  }
+  {
+    TraceRange r(kTake[dim]);
+    run(take);
+    debug_phase(stream, device, kTake[dim]);
+  }
+  {
+    TraceRange r(kComm[dim]);
+    transport->exchange(recvs, sends, device, stream);
+    debug_phase(stream, device, kComm[dim]);
+  }
+  TraceRange r(kAdd[dim]);
+  run(first);
+  run(second);
+  debug_phase(stream, device, kAdd[dim]);
+}
+
+}  // namespace igg

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 
+#include "igg/accum.hpp"
 #include "igg/copy.hpp"
 
 namespace igg {
@@ -161,6 +162,148 @@ void host_copy3d(const std::vector<Copy3D>& copies, int elem_bytes) {
                         c.n_inner, c.src_sm, c.src_si, c.dst_sm, c.dst_si});
   }
   host_copy2d(planes, elem_bytes);
+}
+
+// ---------------------------------------------------------------- accumulation
+//
+// Host equivalent of accum3d_batch_kernel (igg/accum.hpp): the reference the
+// GPU result is compared with bit for bit, and the data path of
+// accumulate_halo_ for CPU fields. Half and bfloat16 add the way torch does on
+// the CPU: in float, rounded once to the storage type.
+namespace {
+
+struct Half { uint16_t bits; };
+struct BFloat { uint16_t bits; };
+
+inline float to_float(BFloat v) {
+  const uint32_t u = static_cast<uint32_t>(v.bits) << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+inline BFloat to_bfloat(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return {static_cast<uint16_t>(0x7fc0u)};  // NaN
+  u += 0x7fffu + ((u >> 16) & 1u);  // to nearest, ties to even
+  return {static_cast<uint16_t>(u >> 16)};
+}
+inline float to_float(Half v) {
+  const uint32_t s = static_cast<uint32_t>(v.bits & 0x8000u) << 16;
+  uint32_t e = (v.bits >> 10) & 0x1fu, m = v.bits & 0x3ffu, u;
+  if (e == 0 && m == 0) {
+    u = s;
+  } else if (e == 0) {  // subnormal: normal in float
+    e = 113;
+    while (!(m & 0x400u)) m <<= 1, --e;
+    u = s | (e << 23) | ((m & 0x3ffu) << 13);
+  } else if (e == 31) {
+    u = s | 0x7f800000u | (m << 13);
+  } else {
+    u = s | ((e + 112) << 23) | (m << 13);
+  }
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+inline Half to_half(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  const uint16_t s = static_cast<uint16_t>((u >> 16) & 0x8000u);
+  u &= 0x7fffffffu;
+  if (u > 0x7f800000u) return {static_cast<uint16_t>(s | 0x7e00u)};   // NaN
+  if (u >= 0x47800000u) return {static_cast<uint16_t>(s | 0x7c00u)};  // >= 2^16 (and inf): inf
+  if (u < 0x33000000u) return {s};                                    // < 2^-25: zero
+  const uint32_t e = u >> 23;
+  uint32_t m = (u & 0x7fffffu) | 0x800000u;  // 24 significant bits
+  // bits to drop: 13 for a normal half (e >= 113), more for a subnormal one
+  const uint32_t drop = e >= 113 ? 13 : 13 + (113 - e);
+  const uint32_t half = 1u << (drop - 1), rest = m & ((1u << drop) - 1);
+  m >>= drop;
+  if (rest > half || (rest == half && (m & 1u))) ++m;  // to nearest, ties to even
+  // (a carry out of the mantissa moves into the exponent field, as it must)
+  const uint32_t h = e >= 113 ? ((e - 113) << 10) + m : m;  // (m holds the implicit bit of a normal half)
+  return {static_cast<uint16_t>(s | h)};
+}
+
+struct C64 { float re, im; };
+struct C128 { double re, im; };
+
+template <typename T>
+inline T add_elem(T a, T b) { return static_cast<T>(a + b); }
+template <>
+inline C64 add_elem(C64 a, C64 b) { return {a.re + b.re, a.im + b.im}; }
+template <>
+inline C128 add_elem(C128 a, C128 b) { return {a.re + b.re, a.im + b.im}; }
+template <>
+inline Half add_elem(Half a, Half b) { return to_half(to_float(a) + to_float(b)); }
+template <>
+inline BFloat add_elem(BFloat a, BFloat b) { return to_bfloat(to_float(a) + to_float(b)); }
+// (integers wrap, as torch's do)
+template <>
+inline int8_t add_elem(int8_t a, int8_t b) { return static_cast<int8_t>(static_cast<uint8_t>(a) + static_cast<uint8_t>(b)); }
+template <>
+inline int16_t add_elem(int16_t a, int16_t b) { return static_cast<int16_t>(static_cast<uint16_t>(a) + static_cast<uint16_t>(b)); }
+template <>
+inline int32_t add_elem(int32_t a, int32_t b) { return static_cast<int32_t>(static_cast<uint32_t>(a) + static_cast<uint32_t>(b)); }
+template <>
+inline int64_t add_elem(int64_t a, int64_t b) { return static_cast<int64_t>(static_cast<uint64_t>(a) + static_cast<uint64_t>(b)); }
+
+template <typename T>
+void accum_rows(const Accum3D& a, int64_t r0, int64_t r1) {
+  const Copy3D& c = a.c;
+  T* src = reinterpret_cast<T*>(const_cast<char*>(c.src));
+  T* dst = reinterpret_cast<T*>(c.dst);
+  const bool adds = static_cast<int>(a.op) & 1, takes = static_cast<int>(a.op) & 2, zero = a.op == AccumOp::Zero;
+  T nought;
+  std::memset(&nought, 0, sizeof(T));  // +0 of every type
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t o = r / c.n_mid, m = r - o * c.n_mid;
+    T* s = src + o * c.src_so + m * c.src_sm;
+    T* d = dst + o * c.dst_so + m * c.dst_sm;
+    for (int64_t i = 0; i < c.n_inner; ++i) {
+      T& dv = d[i * c.dst_si];
+      if (zero) {
+        dv = nought;
+        continue;
+      }
+      T& sv = s[i * c.src_si];
+      dv = adds ? add_elem<T>(dv, sv) : sv;
+      if (takes) sv = nought;
+    }
+  }
+}
+
+template <typename T>
+void accum_typed(const Accum3D& a) {
+  const Copy3D& c = a.c;
+  const int64_t rows = c.n_outer * c.n_mid;
+  if (rows <= 0 || c.n_inner <= 0) return;
+  const int64_t bytes = rows * c.n_inner * static_cast<int64_t>(sizeof(T));
+  if (bytes < THREADCOPY_THRESHOLD || rows < 2) return accum_rows<T>(a, 0, rows);
+  const int64_t grain = std::max<int64_t>(1, rows / (4 * static_cast<int64_t>(pool().size())));
+  host_parallel_for(rows, grain, [&](int64_t r0, int64_t r1) { accum_rows<T>(a, r0, r1); });
+}
+
+}  // namespace
+
+void host_accum3d(const std::vector<Accum3D>& ops, AccumType type) {
+  for (const Accum3D& a : ops) {
+    switch (type) {
+      case AccumType::F32: accum_typed<float>(a); break;
+      case AccumType::F64: accum_typed<double>(a); break;
+      case AccumType::I8: accum_typed<int8_t>(a); break;
+      case AccumType::I16: accum_typed<int16_t>(a); break;
+      case AccumType::I32: accum_typed<int32_t>(a); break;
+      case AccumType::I64: accum_typed<int64_t>(a); break;
+      case AccumType::U8: accum_typed<uint8_t>(a); break;
+      case AccumType::F16: accum_typed<Half>(a); break;
+      case AccumType::BF16: accum_typed<BFloat>(a); break;
+      case AccumType::C64: accum_typed<C64>(a); break;
+      case AccumType::C128: accum_typed<C128>(a); break;
+      default: fail("host_accum3d: unknown element type ", static_cast<int>(type));
+    }
+  }
 }
 
 }  // namespace igg

@@ -32,6 +32,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "igg/accum.hpp"
 #include "igg/comm.hpp"
 #include "igg/peer.hpp"
 #include "igg/copy.hpp"
@@ -167,6 +168,21 @@ class HaloEngine {
   void exchange(const std::vector<Field>& fields, hipStream_t stream, int mode_override = -1);
   // Only the dimension `dim` (0-based); used by tests and pipelined apps.
   void exchange_dim(const std::vector<Field>& fields, int dim, hipStream_t stream);
+  // The transpose of the sequential exchange (accumulate_halo_): dimensions
+  // z -> y -> x; in each, every halo slab that has a neighbour is taken (sent
+  // to that neighbour, then zero) and what arrives is added into the matching
+  // send slab, the left neighbour's message before the right one's. Per
+  // dimension at most one take launch (the non-contiguous halo slabs of all
+  // fields and both sides; contiguous ones are sent in place), one transport
+  // phase (receives into pool buffers) and one launch that adds every message
+  // and zeroes the slabs sent in place - a second, ordered launch takes the
+  // right-hand messages of the fields whose two send slabs share planes
+  // (size < 2*ol). Self-periodic: one add-and-clear launch. Stream-ordered,
+  // no host synchronisation. `dev_transport` moves device messages (not the
+  // engine's own: the adjoint never runs over put); host fields use the
+  // engine's host transport.
+  void accumulate(const std::vector<Field>& fields, AccumType type, hipStream_t stream,
+                  const std::shared_ptr<Transport>& dev_transport);
   void set_mode(HaloMode m) { mode_ = m; }
   HaloMode mode() const { return mode_; }
   void set_pack_mode(int dim, PackMode m) { pack_mode_.at(static_cast<size_t>(dim)) = m; }
@@ -179,6 +195,8 @@ class HaloEngine {
  private:
   void exchange_dim_impl(const std::vector<Field>& fields, int dim, bool device,
                          hipStream_t stream);
+  void accumulate_dim(const std::vector<Field>& fields, AccumType type, int dim, bool device, hipStream_t stream,
+                      const std::shared_ptr<Transport>& transport);
   void exchange_onephase(const std::vector<Field>& fields, bool device, hipStream_t stream);
   void exchange_put(const std::vector<Field>& fields, hipStream_t stream, PeerMesh& mesh);
   // Receive / send regions of the one-phase message with receiver-side

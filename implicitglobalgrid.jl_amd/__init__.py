@@ -19,7 +19,10 @@ over some axes and keeps the others (profiles, column maxima), and
 every n-th cell - from the owned cells (``indices_g``, ``selection_shape_g``;
 parallel/gather_g.py), and its inverse ``scatter_g``, which fills the local
 fields of all ranks from a global array on a root (``scatter_pieces``;
-parallel/scatter_g.py).
+parallel/scatter_g.py); and ``accumulate_halo_``, the transpose of
+``update_halo_``, which adds the halos into the cells of the ranks that own
+them (parallel/accumulate.py), with the differentiable exchange
+``igg.autograd.update_halo`` built on it.
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -32,6 +35,8 @@ from .parallel.grid import (  # noqa: F401
 )
 from .parallel.device import select_device  # noqa: F401
 from .parallel.halo import update_halo, update_halo_  # noqa: F401
+from .parallel.accumulate import accumulate_halo_  # noqa: F401
+from . import autograd  # noqa: F401
 from .parallel.transport_select import select_transport  # noqa: F401
 from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
 from .parallel.gather_g import gather_g, indices_g, selection_shape_g  # noqa: F401
@@ -62,5 +67,5 @@ __all__ = [
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
     "norm_g", "norm_diff_g", "mean_g", "project_g", "gather_g", "indices_g", "selection_shape_g",
-    "scatter_g", "scatter_pieces",
+    "scatter_g", "scatter_pieces", "accumulate_halo_", "autograd",
 ]
