@@ -8,7 +8,8 @@
 // As there, every plane-sized register array has three slots, plane j lives in
 // slot (j - first) % 3, and the loop body is unrolled over the three phases.
 // Within a position the work goes row by row - intermediate-1 (p), then
-// intermediate-2 (p-1), then output (p-2) of row r - and the loads of the next
+// intermediate-2 (p-1, tile rows 1 .. TYE-2 only), then output (p-2, tile rows
+// 2 .. TYE-3 only) of row r - and the loads of the next
 // position follow the last use of the row they replace (T plane p+2 after
 // stage 1, Q plane p+1 after stage 3), so of each intermediate field and of Q
 // two planes and one row are live, not three planes and a fourth of Q.
@@ -60,9 +61,9 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
   // in the two-step body: rowsN is [3][BY][2][W] behind one row of padding
   // (rowsN[RP * slot + lb + k * W], k = 0..3: the last row of the wave below,
   // this wave's first and last row, the first row of the wave above; k = 0 / 3
-  // of the first / last wave is padding or another slot, read only for ring
-  // rows, whose values are never used), zedgeN is [3][TYE][BZ + 1][2]: per row
-  // the values left ([0]) and right ([1]) of every segment boundary.
+  // of the first / last wave is padding or another slot, never read: the tile's
+  // outer rows take part in stage 1 only), zedgeN is [3][TYE][BZ + 1][2]: per
+  // row the values left ([0]) and right ([1]) of every segment boundary.
   constexpr int RP = BY * 2 * W;
   __shared__ __attribute__((aligned(16))) T rows1[3 * RP + 2 * W];
   __shared__ __attribute__((aligned(16))) T rows2[3 * RP + 2 * W];
@@ -79,7 +80,12 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
 
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wz = wid % BZ, wy = wid / BZ;
+  // Wave wid takes rows wy * RY .. of the tile and segment wz of the row; the
+  // odd wy take their segments rotated by BZ/2. Waves s and s + 4 usually share
+  // a SIMD, and the workgroup moves at the pace of its slowest SIMD (one barrier
+  // per position): so a wave that holds an end of the row, the only kind that
+  // selects (`wplain` below), shares its SIMD with one that holds none.
+  const int wy = wid / BZ, wz = (wid + (wy & 1) * (BZ / 2)) % BZ;
   const int n0 = static_cast<int>(a.n0), n1 = static_cast<int>(a.n1), n2 = static_cast<int>(a.n2);
   const uint32_t s1b = n2 * ES, s0b = n1 * s1b;  // row / plane stride in bytes
   const int zw = wz * WS;                        // segment origin (wave-uniform)
@@ -111,15 +117,27 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
 
   // Rows outside the array alias row 0 / n1-1 (boundary rows: never written).
   uint32_t rowo[RY];  // wave-uniform row offsets (bytes)
-  bool rbnd[RY], rout[RY];
+  uint32_t rbnd = 0, rout = 0;  // bit r: row r is a boundary row / is written
 #pragma unroll
   for (int r = 0; r < RY; ++r) {
     const int yr = ye0 + wy * RY + r;
     const int lr = wy * RY + r;
     rowo[r] = min(max(yr, 0), n1 - 1) * s1b;
-    rbnd[r] = yr <= 0 || yr >= n1 - 1;
-    rout[r] = lr >= 2 && lr <= TYE - 3 && yr <= n1 - 2;
+    rbnd |= (yr <= 0 || yr >= n1 - 1 ? 1u : 0u) << r;
+    rout |= (lr >= 2 && lr <= TYE - 3 && yr <= n1 - 2 ? 1u : 0u) << r;
   }
+  // Stage 2 (intermediate-2) is wanted on tile rows 1 .. TYE-2, stage 3 on rows
+  // 2 .. TYE-3: row 0 of the first wave along y and row RY-1 of the last are
+  // formed in stage 1 alone, and nothing of them is shared.
+  const bool ylo = wy != 0, yhi = wy != BY - 1;
+  // The plain class of waves: no lane holds an end of the row (z = 0 or n2-1)
+  // and no row is a boundary row, so on an inner plane no point of the wave
+  // keeps T's value. Lanes past the row do not count: no value of theirs
+  // reaches a stored point.
+  uint64_t zbm[VZ], zanym = 0;  // zb as lane masks: what the selects take
+#pragma unroll
+  for (int e = 0; e < VZ; ++e) zanym |= zbm[e] = __ballot(zb[e]);
+  const bool wplain = (zanym & __ballot(zin)) == 0 && rbnd == 0;
   const uint32_t rowm = min(max(ye0 + wy * RY - 1, 0), n1 - 1) * s1b;
   const uint32_t rowp = min(max(ye0 + wy * RY + RY, 0), n1 - 1) * s1b;
 
@@ -171,9 +189,14 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
 
   // One stencil update of row r of a plane held in registers `cc` (its x
   // neighbours xm / xp), whose parts beyond the wave come from `yv` / `yn`
-  // (rows) and `zl` (the edge lanes' z neighbour).
-  auto update = [&](const V& c, const V& xm, const V& xp, const V& yv, const V& yn, T zl, const V& q, bool keep)
-                    __attribute__((always_inline)) {
+  // (rows) and `zl` (the edge lanes' z neighbour). A point on the boundary keeps
+  // c: a z-boundary point by a select on its lane mask, a boundary plane or row
+  // (`keep`, wave-uniform) as a whole. A `plain` update (wave-uniform) holds no
+  // such point and skips both: one scalar branch where the selects were. The
+  // empty asm statements cannot be speculated, which keeps the compiler from
+  // folding the branches back into selects that every wave would execute.
+  auto update = [&](bool plain, const V& c, const V& xm, const V& xp, const V& yv, const V& yn, T zl, const V& q,
+                    bool keep) __attribute__((always_inline)) {
     const T prev = lane_shift_keep<0x138>(zl, c[VZ - 1]);  // wave_shr:1, lane 0 keeps zl
     const T next = lane_shift_keep<0x130>(zl, c[0]);       // wave_shl:1, lane 63 keeps zl
     V out;
@@ -181,8 +204,16 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
     for (int e = 0; e < VZ; ++e) {
       const T zm = e == 0 ? prev : c[e > 0 ? e - 1 : 0];
       const T zp = e == VZ - 1 ? next : c[e + 1 < VZ ? e + 1 : e];
-      const T v = diffusion_point_q(c[e], xm[e], xp[e], yv[e], yn[e], zm, zp, q[e], rdx2, rdy2, rdz2);
-      out[e] = (keep | zb[e]) ? c[e] : v;  // no short circuit: one select, no branch on the uniform part
+      out[e] = diffusion_point_q(c[e], xm[e], xp[e], yv[e], yn[e], zm, zp, q[e], rdx2, rdy2, rdz2);
+    }
+    if (!plain) {  // wave-uniform
+      asm volatile("");
+#pragma unroll
+      for (int e = 0; e < VZ; ++e) out[e] = __builtin_amdgcn_inverse_ballot_w64(zbm[e]) ? c[e] : out[e];
+      if (keep) {  // rare
+        asm volatile("");
+        out = c;
+      }
     }
     return out;
   };
@@ -190,6 +221,7 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
   // One march position at phase PH = (p - p0) % 3.
   auto position = [&](auto phase, const int p) __attribute__((always_inline)) {
     constexpr int PH = decltype(phase)::value;
+    const bool plain = wplain && p > 1 && p < n0 - 1;  // neither stage 1 nor stage 2 is on a boundary plane
     constexpr int SA = (PH + 2) % 3, SB = PH, SN = (PH + 1) % 3;  // slots of planes p-1 (and p-4), p (p-3), p+1 (p-2)
     const bool pb1 = p <= 0 || p >= n0 - 1;      // boundary plane: the intermediate value is T's
     const bool pb2 = p - 1 <= 0 || p >= n0;
@@ -204,7 +236,7 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
       {
         const V& yv = (r == 0) ? ym : tt[SB][r > 0 ? r - 1 : 0];
         const V& yn = (r == RY - 1) ? yp : tt[SB][r + 1 < RY ? r + 1 : r];
-        i1[SB][r] = update(tt[SB][r], tt[SA][r], tt[SN][r], yv, yn, ev[r], qq[SB][r], pb1 | rbnd[r]);
+        i1[SB][r] = update(plain, tt[SB][r], tt[SA][r], tt[SN][r], yv, yn, ev[r], qq[SB][r], pb1 | ((rbnd >> r) & 1) != 0);
         tt[SA][r] = ldg<V>(t2 + rowo[r], vo);
         // T of plane p+1 around the wave's rows and segment, behind the use of plane p's
         if (r == 0) ym = ldg<V>(t1 + rowm, vo);
@@ -213,23 +245,25 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
 #pragma unroll
           for (int h = 0; h < RY / 2; ++h) ev[h] = ldg<T>(t1 + rowo[h], voe);
         }
+      }
+      // 2. intermediate-2 plane p-1 from intermediate-1 planes p-2, p-1, p; not
+      // for the tile's outer rows (wave-uniform), whose intermediate-1 values
+      // no other wave reads either
+      if ((r > 0 || ylo) && (r < RY - 1 || yhi)) {
         if (r == 0) *reinterpret_cast<V*>(&rows1[RP * SB + lb + W]) = i1[SB][r];
         if (r == RY - 1) *reinterpret_cast<V*>(&rows1[RP * SB + lb + 2 * W]) = i1[SB][r];
-      }
-      // 2. intermediate-2 plane p-1 from intermediate-1 planes p-2, p-1, p
-      {
         V yv, yn;
         if (r == 0) yv = *reinterpret_cast<const V*>(&rows1[RP * SA + lb]);
         else yv = i1[SA][r > 0 ? r - 1 : 0];
         if (r == RY - 1) yn = *reinterpret_cast<const V*>(&rows1[RP * SA + lb + 3 * W]);
         else yn = i1[SA][r + 1 < RY ? r + 1 : r];
         const T zl = zedge1[ZP * SA + r * ZR + zx];  // every lane reads; the edge lanes use it
-        i2[SA][r] = update(i1[SA][r], i1[SN][r], i1[SB][r], yv, yn, zl, qq[SA][r], pb2 | rbnd[r]);
+        i2[SA][r] = update(plain, i1[SA][r], i1[SN][r], i1[SB][r], yv, yn, zl, qq[SA][r], pb2 | ((rbnd >> r) & 1) != 0);
         if (r == 0) *reinterpret_cast<V*>(&rows2[RP * SA + lb + W]) = i2[SA][r];
         if (r == RY - 1) *reinterpret_cast<V*>(&rows2[RP * SA + lb + 2 * W]) = i2[SA][r];
       }
       // 3. output plane p-2 from intermediate-2 planes p-3, p-2, p-1
-      if (st && rout[r]) {  // wave-uniform
+      if (st && ((rout >> r) & 1) != 0) {  // wave-uniform
         V yv, yn;
         if (r == 0) yv = *reinterpret_cast<const V*>(&rows2[RP * SN + lb]);
         else yv = i2[SN][r > 0 ? r - 1 : 0];
@@ -237,7 +271,7 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
         else yn = i2[SN][r + 1 < RY ? r + 1 : r];
         const T zl = zedge2[ZP * SN + r * ZR + zx];
         // z boundary: T's value (written only with halo_z)
-        const V out = update(i2[SN][r], i2[SB][r], i2[SA][r], yv, yn, zl, qq[SN][r], false);
+        const V out = update(plain, i2[SN][r], i2[SB][r], i2[SA][r], yv, yn, zl, qq[SN][r], false);
         T* dst = reinterpret_cast<T*>(ob + rowo[r] + here(vo));
         if (wvst) {  // wave-uniform: one masked region
           if (vst) __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
@@ -253,15 +287,26 @@ __device__ __forceinline__ void body(const K2Args<T>& a) {
       qq[SN][r] = ldg<V>(q1 + rowo[r], vo);
     }
     // the edge lanes, one masked region: the other half of the edge values of
-    // plane p+1, and their own values of both new planes for the neighbours
+    // plane p+1, and their own values of both new planes for the neighbours.
+    // Stage 2 reads intermediate-1 on tile rows 1 .. TYE-2, stage 3 reads
+    // intermediate-2 on rows 2 .. TYE-3: `cls` = which of ylo (1) / yhi (2) a
+    // row of the wave needs to be among them.
     if (ledge) {
 #pragma unroll
       for (int h = RY / 2; h < RY; ++h) ev[h] = ldg<T>(t1 + rowo[h], voe);
+      auto share = [&](auto cls) __attribute__((always_inline)) {
 #pragma unroll
-      for (int r = 0; r < RY; ++r) {
-        zedge1[ZP * SB + r * ZR + zo] = l63 ? i1[SB][r][VZ - 1] : i1[SB][r][0];
-        zedge2[ZP * SA + r * ZR + zo] = l63 ? i2[SA][r][VZ - 1] : i2[SA][r][0];
-      }
+        for (int r = 0; r < RY; ++r) {
+          if ((r < 1 ? 1 : 0) + (r > RY - 2 ? 2 : 0) == decltype(cls)::value)
+            zedge1[ZP * SB + r * ZR + zo] = l63 ? i1[SB][r][VZ - 1] : i1[SB][r][0];
+          if ((r < 2 ? 1 : 0) + (r > RY - 3 ? 2 : 0) == decltype(cls)::value)
+            zedge2[ZP * SA + r * ZR + zo] = l63 ? i2[SA][r][VZ - 1] : i2[SA][r][0];
+        }
+      };
+      share(std::integral_constant<int, 0>{});
+      if (ylo) share(std::integral_constant<int, 1>{});
+      if (yhi) share(std::integral_constant<int, 2>{});
+      if (ylo && yhi) share(std::integral_constant<int, 3>{});
     }
     __syncthreads();
 

@@ -18,13 +18,23 @@
 // are written, and tiles advance by TYE-4 rows. At march position p a wave
 //   1. forms intermediate-1 plane p from T planes p-1, p, p+1 (y neighbours
 //      beyond the wave's rows and the segment-edge z values are loaded);
-//   2. forms intermediate-2 plane p-1 from intermediate-1 planes p-2, p-1, p;
-//   3. forms output plane p-2 from intermediate-2 planes p-3, p-2, p-1;
+//   2. forms intermediate-2 plane p-1 from intermediate-1 planes p-2, p-1, p,
+//      on all but the tile's two outer rows (rows 0 and TYE-1 feed nothing);
+//   3. forms output plane p-2 from intermediate-2 planes p-3, p-2, p-1, on the
+//      TYE-4 written rows;
 //   4. issues the loads of position p+1 (T plane p+2, Q plane p+1).
 // Each wave's first and last row and its segment-edge z values of both
 // intermediate fields travel through LDS (one buffer per phase of the march
 // and field), with one barrier per position. An x chunk [xs, xe) starts with
 // the four-position lead-in p = xs-2 .. xs+1.
+//
+// Waves: wave wid owns rows (wid / BZ) * RY .. of the tile and one 64-lane
+// segment of the row; the odd rows of waves take their segments rotated by
+// BZ/2 (wz = (wid + (wy & 1) * BZ/2) % BZ). Only a wave that holds an end of
+// the row (z = 0 or n2-1), a boundary row or a boundary plane selects between
+// T's value and the update; the others take a select-free path behind one
+// wave-uniform branch per row update, and the rotation gives every SIMD one
+// wave of either kind (waves s and s+4 usually share SIMD s).
 //
 // The kernel body is igg/stencil3_impl.hpp.
 #include <hip/hip_runtime.h>
