@@ -27,6 +27,7 @@
 #include "igg/ipc.hpp"
 #include "igg/project.hpp"
 #include "igg/reduce.hpp"
+#include "igg/sample.hpp"
 #include "igg/select.hpp"
 #include "igg/stencil.hpp"
 #include "igg/topology.hpp"
@@ -59,6 +60,50 @@ std::vector<SelectDesc> select_descs(const std::vector<SelectTuple>& jobs) {
     v.push_back(j);
   }
   return v;
+}
+
+// sample_g's arguments as Python passes them: per dimension (E, periodic, m,
+// [(g0, g1, i0), ...]), per field (pointer, strides in elements).
+using SampleDimTuple = std::tuple<int64_t, int, int64_t, std::vector<std::array<int64_t, 3>>>;
+using SampleFieldTuple = std::pair<uintptr_t, std::vector<int64_t>>;
+
+// One SampleArgs per SAMPLE_MAX_FIELDS fields, each handed to `run`.
+template <typename Run>
+void sample_calls(const char* who, const std::vector<SampleDimTuple>& dims, const std::vector<SampleFieldTuple>& fields,
+                  uintptr_t points, int64_t ps0, int64_t ps1, int64_t npts, uintptr_t out, int64_t out_fs, bool me0,
+                  uintptr_t row, int64_t nrows, int64_t row_stride, Run run) {
+  SampleArgs a;
+  a.nd = static_cast<int32_t>(dims.size());
+  if (a.nd < 1 || a.nd > 3) fail(who, ": fields must have 1 to 3 dimensions (got ", dims.size(), ")");
+  if (fields.empty()) fail(who, ": at least one field is needed");
+  for (int d = 0; d < a.nd; ++d) {
+    SampleDim& D = a.dim[d];
+    const auto& segs = std::get<3>(dims[d]);
+    if (segs.size() > 2) fail(who, ": at most two owned segments per dimension");
+    auto narrow = [&](int64_t v) {
+      if (v < 0 || v > INT32_MAX) fail(who, ": ", v, " in the table of dimension ", d, " is negative or above 2^31 - 1");
+      return static_cast<int32_t>(v);
+    };
+    D.E = narrow(std::get<0>(dims[d])), D.per = std::get<1>(dims[d]) ? 1 : 0, D.m = narrow(std::get<2>(dims[d]));
+    D.nseg = static_cast<int32_t>(segs.size());
+    for (int s = 0; s < D.nseg; ++s)
+      D.g0[s] = narrow(segs[s][0]), D.g1[s] = narrow(segs[s][1]), D.i0[s] = narrow(segs[s][2]);
+  }
+  a.me0 = me0 ? 1 : 0;
+  a.P = reinterpret_cast<const double*>(points), a.ps0 = ps0, a.ps1 = ps1, a.npts = npts;
+  a.out_fs = out_fs;
+  a.row = reinterpret_cast<const int64_t*>(row), a.nrows = nrows, a.row_stride = row_stride;
+  for (size_t f0 = 0; f0 < fields.size(); f0 += SAMPLE_MAX_FIELDS) {
+    a.nf = static_cast<int32_t>(std::min<size_t>(fields.size() - f0, SAMPLE_MAX_FIELDS));
+    for (int f = 0; f < a.nf; ++f) {
+      const auto& [ptr, strides] = fields[f0 + f];
+      if (static_cast<int>(strides.size()) != a.nd) fail(who, ": one stride per dimension of the field");
+      a.field[f].base = reinterpret_cast<const void*>(ptr);
+      for (int d = 0; d < 3; ++d) a.field[f].stride[d] = d < a.nd ? strides[d] : 0;
+    }
+    a.out = reinterpret_cast<uint64_t*>(out) + static_cast<int64_t>(f0) * out_fs;
+    run(a);
+  }
 }
 
 // DLPack (v0.8 ABI, the layout torch.utils.dlpack consumes): a native device
@@ -713,6 +758,40 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("jobs"), py::arg("stream") = 0,
         "dst[i0*T0 + i1*T1 + i2*T2] (f64, device) = double(src[i0*S0 + i1*S1 + i2*S2]) (f32, device), i_d < c_d, for "
         "every job (src, dst, counts, src strides, dst strides); strides in elements. The plan is select_plan's.");
+
+  // --- point sampling (parallel/sample_g.py)
+  m.attr("SAMPLE_BLOCK") = SAMPLE_BLOCK;
+  m.attr("SAMPLE_POINTS") = SAMPLE_POINTS;
+  m.attr("SAMPLE_MAX_BLOCKS") = SAMPLE_MAX_BLOCKS;
+  m.attr("SAMPLE_MAX_FIELDS") = SAMPLE_MAX_FIELDS;
+  m.def("sample",
+        [](const std::vector<SampleDimTuple>& dims, const std::vector<SampleFieldTuple>& fields, int elem_size,
+           uintptr_t points, int64_t ps0, int64_t ps1, int64_t npts, uintptr_t out, int64_t out_fs, bool me0,
+           uintptr_t row, int64_t nrows, int64_t row_stride, uintptr_t stream, int max_blocks) {
+          sample_calls("sample", dims, fields, points, ps0, ps1, npts, out, out_fs, me0, row, nrows, row_stride,
+                       [&](const SampleArgs& a) { sample(a, elem_size, max_blocks, as_stream(stream)); });
+        },
+        py::arg("dims"), py::arg("fields"), py::arg("elem_size"), py::arg("points"), py::arg("ps0"), py::arg("ps1"),
+        py::arg("npts"), py::arg("out"), py::arg("out_fs"), py::arg("me0"), py::arg("row") = 0, py::arg("nrows") = 0,
+        py::arg("row_stride") = 0, py::arg("stream") = 0, py::arg("max_blocks") = 0,
+        "out[f*out_fs + p] (f64 bits, device) = field f (f32 / f64, device; (pointer, strides in elements)) "
+        "interpolated multilinearly at point p, whose coordinate of axis d is the double at points[p*ps0 + d*ps1], in "
+        "the field's global index space. dims: per axis (E, periodic, m, [(g0, g1, i0), ...]) - the global extent, "
+        "the local size and this rank's owned segments. A point whose cell this rank does not own gives 0 bits, an "
+        "invalid point the canonical quiet NaN if me0 and 0 otherwise. With `row` (a device int64) the output moves "
+        "by *row * row_stride elements and nothing is written if *row >= nrows. One launch per SAMPLE_MAX_FIELDS "
+        "fields; max_blocks caps the grid (0: SAMPLE_MAX_BLOCKS).");
+  m.def("host_sample",
+        [](const std::vector<SampleDimTuple>& dims, const std::vector<SampleFieldTuple>& fields, int elem_size,
+           uintptr_t points, int64_t ps0, int64_t ps1, int64_t npts, uintptr_t out, int64_t out_fs, bool me0,
+           uintptr_t row, int64_t nrows, int64_t row_stride) {
+          sample_calls("host_sample", dims, fields, points, ps0, ps1, npts, out, out_fs, me0, row, nrows, row_stride,
+                       [&](const SampleArgs& a) { host_sample(a, elem_size); });
+        },
+        py::arg("dims"), py::arg("fields"), py::arg("elem_size"), py::arg("points"), py::arg("ps0"), py::arg("ps1"),
+        py::arg("npts"), py::arg("out"), py::arg("out_fs"), py::arg("me0"), py::arg("row") = 0, py::arg("nrows") = 0,
+        py::arg("row_stride") = 0,
+        "`sample` on host memory with the same expressions: the CPU path and the GPU tests' reference.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

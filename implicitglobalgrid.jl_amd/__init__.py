@@ -22,7 +22,10 @@ fields of all ranks from a global array on a root (``scatter_pieces``;
 parallel/scatter_g.py); and ``accumulate_halo_``, the transpose of
 ``update_halo_``, which adds the halos into the cells of the ranks that own
 them (parallel/accumulate.py), with the differentiable exchange
-``igg.autograd.update_halo`` built on it.
+``igg.autograd.update_halo`` built on it; and ``sample_g``, the fields' values
+at arbitrary points of the global grid, interpolated by the rank that owns
+each point's cell, with ``Recorder`` for time series of them
+(``sample_owner``, ``index_g``; parallel/sample_g.py).
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401
@@ -41,6 +44,7 @@ from .parallel.transport_select import select_transport  # noqa: F401
 from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
 from .parallel.gather_g import gather_g, indices_g, selection_shape_g  # noqa: F401
 from .parallel.scatter_g import scatter_g, scatter_pieces  # noqa: F401
+from .parallel.sample_g import Recorder, index_g, sample_g, sample_owner  # noqa: F401
 from .utils.tools import coords_g, nx_g, ny_g, nz_g, tic, toc, x_g, y_g, z_g  # noqa: F401
 from .utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .ops.reduce import (  # noqa: F401
@@ -67,5 +71,5 @@ __all__ = [
     "IGGError", "coords_g", "gather_async_", "save_checkpoint", "load_checkpoint", "select_transport",
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
     "norm_g", "norm_diff_g", "mean_g", "project_g", "gather_g", "indices_g", "selection_shape_g",
-    "scatter_g", "scatter_pieces", "accumulate_halo_", "autograd",
+    "scatter_g", "scatter_pieces", "accumulate_halo_", "autograd", "sample_g", "sample_owner", "index_g", "Recorder",
 ]

@@ -22,6 +22,7 @@ SECTIONS = [
     ("Gather", "igg", ["gather_", "gather_async_"]),
     ("The global field: whole, sliced or coarsened", "igg", ["gather_g", "selection_shape_g", "indices_g"]),
     ("A global array into the fields", "igg", ["scatter_g", "scatter_pieces"]),
+    ("Values at points of the global grid", "igg", ["sample_g", "index_g", "sample_owner", "Recorder"]),
     ("Global sizes and coordinates, timing", "igg",
      ["nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "coords_g", "tic", "toc"]),
     ("Global reductions", "igg",
