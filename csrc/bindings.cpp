@@ -1216,6 +1216,21 @@ PYBIND11_MODULE(_igg_native, m) {
           return diffusion3d_threestep_ok(a);
         },
         py::arg("n"), py::arg("elem_bytes"), py::arg("form") = 0);
+  // (tiles, planes per x chunk, workgroups) of a launch of `form` on shape n aiming at `target` workgroups:
+  // host arithmetic. _target: what a launch with `rounds` aims at (rounds > 0 asks the device).
+  m.def("diffusion3d_threestep_plan",
+        [](const Int3& n, int form, int64_t target) {
+          DiffusionArgs a{0, 0, 0, {n[0], n[1], n[2]}, {1.0, 1.0, 1.0}, 0.0, 8, 0, false, form, 1};
+          const ThreestepPlan p = diffusion3d_threestep_plan(a, target);
+          return std::make_tuple(p.tiles, p.chunk, p.workgroups);
+        },
+        py::arg("n"), py::arg("form"), py::arg("target"));
+  m.def("diffusion3d_threestep_target",
+        [](int elem_bytes, int form, int rounds) {
+          DiffusionArgs a{0, 0, 0, {3, 3, 4}, {1.0, 1.0, 1.0}, 0.0, elem_bytes, rounds, false, form, 1};
+          return diffusion3d_threestep_target(a);
+        },
+        py::arg("elem_bytes"), py::arg("form"), py::arg("rounds") = 0);
   m.def("diffusion3d_threestep_forms", []() {
     std::vector<std::string> v;
     for (int i = 0; i < diffusion3d_threestep_num_forms(); ++i) v.push_back(diffusion3d_threestep_form_name(i));

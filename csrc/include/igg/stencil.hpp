@@ -95,6 +95,16 @@ int diffusion3d_threestep_num_forms();
 const char* diffusion3d_threestep_form_name(int form);
 bool diffusion3d_threestep_ok(const DiffusionArgs& a);
 void launch_diffusion3d_threestep(const DiffusionArgs& a, hipStream_t stream);
+// How a launch of form a.form covers an a.n field with a grid of about `target`
+// workgroups: tiles along dim 1 (each writes by * ry - 4 rows), planes per x
+// chunk, workgroups = tiles x chunks. Host arithmetic only (no device needed).
+// _target: the workgroups a launch with a.rounds aims at (a.elem_bytes picks
+// the kernel; asks the device for the kernel's residency where rounds > 0).
+struct ThreestepPlan {
+  int64_t tiles, chunk, workgroups;
+};
+ThreestepPlan diffusion3d_threestep_plan(const DiffusionArgs& a, int64_t target);
+int64_t diffusion3d_threestep_target(const DiffusionArgs& a);
 
 // Fused halo exchange (see fused.hpp): the inner-box update additionally
 // stores its send planes into the receivers' arena regions (`out`, 0 = no

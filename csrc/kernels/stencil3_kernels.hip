@@ -36,6 +36,16 @@
 // wave-uniform branch per row update, and the rotation gives every SIMD one
 // wave of either kind (waves s and s+4 usually share SIMD s).
 //
+// Form 1 (Q in LDS): a wave holds of Q only the plane stage 1 reads; the lane
+// parks each value in an LDS slot of its own after stage 1 and reads it back
+// for stages 2 and 3 (no barrier: nobody else touches the slot). T's values
+// around a wave's rows and segment come from the neighbouring waves' registers
+// through LDS as well, one position ahead, as those of the intermediate fields
+// do; only the row beyond the tile is loaded. The registers that frees go into
+// a fifth row per wave: a 10-row tile writes 6 rows, 4.0 row updates per
+// written row and pass instead of 4.5, and every row of T and Q is pulled from
+// L2 2.0 and 1.67 times per written row instead of 2.5 and 2.0.
+//
 // The kernel body is igg/stencil3_impl.hpp.
 #include <hip/hip_runtime.h>
 
@@ -52,28 +62,48 @@ diffusion3d_threestep_kernel(const K2Args<T> a) {
   threestep::body<T, BY, RY, VZ, BZ>(a);
 }
 
+template <typename T, int BY, int RY, int VZ, int BZ>
+__global__ void __launch_bounds__(64 * BY * BZ)
+diffusion3d_threestep_qlds_kernel(const K2Args<T> a) {
+  threestep::body_qlds<T, BY, RY, VZ, BZ>(a);
+}
+
 struct Form {
   const char* name;
   int by, ry, bz;
+  bool qlds;  // Q parked in LDS between the stages
 };
 
 // Lanes hold 16 bytes, as in the two-step pass: form 0 spans a 512-point f64 /
 // 1024-point f32 row.
 constexpr Form FORMS[] = {
-    {"t3_by2_ry4_bz4", 2, 4, 4},  // 0: 8 rows x 512 (f64) tile, 4 rows written, 512 threads
+    {"t3_by2_ry4_bz4", 2, 4, 4, false},      // 0: 8 rows x 512 (f64) tile, 4 rows written, 512 threads, 116 KiB LDS
+    {"t3_by2_ry5_bz4_qlds", 2, 5, 4, true},  // 1: 10 rows x 512 (f64) tile, 6 rows written, 512 threads, 143 KiB LDS
 };
 constexpr int NFORMS = sizeof(FORMS) / sizeof(FORMS[0]);
 
-template <typename T, int BY, int RY, int BZ>
-void launch3(const DiffusionArgs& a, hipStream_t stream) {
+template <typename T, int BY, int RY, int BZ, bool QL>
+auto kernel3() {
   constexpr int VZ = 16 / static_cast<int>(sizeof(T));
-  threestep::launch_form<T, BY, RY, BZ>(&diffusion3d_threestep_kernel<T, BY, RY, VZ, BZ>, a, stream);
+  if constexpr (QL) return &diffusion3d_threestep_qlds_kernel<T, BY, RY, VZ, BZ>;
+  else return &diffusion3d_threestep_kernel<T, BY, RY, VZ, BZ>;
+}
+
+// What a form does: launch (stream) or, with stream == nullptr and `target`
+// set, only report the workgroups a launch with a.rounds aims at.
+template <typename T, int BY, int RY, int BZ, bool QL = false>
+void launch3(const DiffusionArgs& a, hipStream_t stream, int64_t* target) {
+  if (target)
+    *target = diffusion3d_target_blocks(reinterpret_cast<const void*>(kernel3<T, BY, RY, BZ, QL>()), 64 * BY * BZ, a.rounds);
+  else
+    threestep::launch_form<T, BY, RY, BZ>(kernel3<T, BY, RY, BZ, QL>(), a, stream);
 }
 
 template <typename T>
-void dispatch3(const DiffusionArgs& a, hipStream_t s) {
+void dispatch3(const DiffusionArgs& a, hipStream_t s, int64_t* target = nullptr) {
   switch (a.form) {
-    case 0: launch3<T, 2, 4, 4>(a, s); break;
+    case 0: launch3<T, 2, 4, 4>(a, s, target); break;
+    case 1: launch3<T, 2, 5, 4, true>(a, s, target); break;
     default: fail("diffusion3d_threestep: no form ", a.form);
   }
 }
@@ -96,6 +126,20 @@ bool diffusion3d_threestep_ok(const DiffusionArgs& a) {
   // the kernel's indices and its byte offsets within a plane are 32-bit
   const int64_t lim = int64_t(1) << 31;
   return a.n[0] < lim - 8 && a.n[1] < lim - 8 && a.n[1] * a.n[2] < lim / a.elem_bytes;
+}
+
+ThreestepPlan diffusion3d_threestep_plan(const DiffusionArgs& a, int64_t target) {
+  if (a.form < 0 || a.form >= NFORMS) fail("diffusion3d_threestep: no form ", a.form);
+  if (a.n[0] < 3 || a.n[1] < 3) fail("diffusion3d_threestep: every extent must be >= 3");
+  return threestep::plan(a.n[0], a.n[1], FORMS[a.form].by * FORMS[a.form].ry - 4, target);
+}
+
+int64_t diffusion3d_threestep_target(const DiffusionArgs& a) {
+  int64_t target = 0;
+  if (a.elem_bytes == 8) dispatch3<double>(a, nullptr, &target);
+  else if (a.elem_bytes == 4) dispatch3<float>(a, nullptr, &target);
+  else fail("diffusion3d_threestep: 4 or 8 bytes per element");
+  return target;
 }
 
 void launch_diffusion3d_threestep(const DiffusionArgs& a, hipStream_t stream) {

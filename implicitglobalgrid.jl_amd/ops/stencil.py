@@ -287,14 +287,17 @@ def time_twostep_pingpong(T2, T, Cp, rd2, dtlam, boxes, single, candidates, step
     return med.pop(None), med
 
 
-# Tilings of the three-step pass (csrc/kernels/stencil3_kernels.hip).
+# Tilings of the three-step pass (csrc/kernels/stencil3_kernels.hip): 0 = tiles
+# of 8 rows that write 4, Q in registers; 1 = tiles of 10 rows that write 6, Q
+# parked in LDS between the stages. Both span a row of 512 float64 / 1024
+# float32 points and leave the same bits.
 THREESTEP_FORMS = tuple(range(len(native.diffusion3d_threestep_forms())))
 
 
 def threestep_ok(T, form: int = 0) -> bool:
     """Whether three-step form ``form`` can run on ``T``: what ``twostep_ok``
     asks, and rows no longer than the form's tile (512 float64 / 1024 float32
-    points for form 0). The pass also needs the quotient array."""
+    points for forms 0 and 1). The pass also needs the quotient array."""
     if not (T.is_cuda and T.dim() == 3 and T.is_contiguous() and T.dtype in (torch.float32, torch.float64)):
         return False
     return bool(native.diffusion3d_threestep_ok(list(T.shape), T.element_size(), int(form)))
@@ -308,7 +311,11 @@ def diffusion3d_threestep_(T2, T, Cp, *, Q, lam: float, dt: float, dx: float, dy
     equal ``T``'s. The pass reads ``T`` and ``Q``, the array ``quotient_`` left
     for this ``Cp`` and ``dt * lam`` (required: it has no dividing form);
     ``Cp`` is only checked against. ``T2``'s boundary planes are not written
-    (``halo_z`` as in ``diffusion3d_``). GPU only; raises ``IGGError``, before
+    (``halo_z`` as in ``diffusion3d_``). ``form`` picks the tiling
+    (``THREESTEP_FORMS``), ``rounds`` the grid as in ``diffusion3d_``;
+    ``native.diffusion3d_threestep_plan(shape, form, target)`` gives the tiles,
+    planes per x chunk and workgroups of a launch that aims at ``target``
+    workgroups. GPU only; raises ``IGGError``, before
     anything is written, where ``threestep_ok`` is false or ``Q`` is missing
     (callers then run the two-step pass or single steps)."""
     _check(T2, T, Cp)
