@@ -1155,6 +1155,35 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("t2"), py::arg("t"), py::arg("cp"), py::arg("n"), py::arg("rd2"), py::arg("dtlam"),
         py::arg("elem_bytes"), py::arg("boxes"), py::arg("device"), py::arg("variant") = 0,
         py::arg("stream") = 0, py::arg("rounds") = 0, py::arg("halo_z") = false);
+  // Transpose of the step (stencil_adj_kernels.hip / stencil_adj_host.cpp): gT = S^T g
+  // where gt != 0, the derivative with respect to Cp where gcp != 0.
+  m.def("diffusion3d_adjoint",
+        [](uintptr_t gt, uintptr_t gcp, uintptr_t g, uintptr_t cp, uintptr_t q, uintptr_t t, const Int3& n,
+           const std::array<double, 3>& rd2, double dtlam, int elem_bytes, bool accumulate, bool device,
+           uintptr_t stream, int chunk) {
+          TraceRange tr("igg.diffusion3d_adjoint");
+          DiffusionAdjointArgs a;
+          a.gt = gt, a.gcp = gcp, a.g = g, a.cp = cp, a.q = q, a.t = t;
+          for (int d = 0; d < 3; ++d) a.n[d] = n[d], a.rd2[d] = rd2[d];
+          a.dt_lam = dtlam, a.elem_bytes = elem_bytes, a.accumulate = accumulate, a.chunk = chunk;
+          if (device) {
+            launch_diffusion3d_adjoint(a, as_stream(stream));
+          } else {
+            py::gil_scoped_release nogil;
+            host_diffusion3d_adjoint(a);
+          }
+        },
+        py::arg("gt"), py::arg("gcp"), py::arg("g"), py::arg("cp"), py::arg("q"), py::arg("t"), py::arg("n"),
+        py::arg("rd2"), py::arg("dtlam"), py::arg("elem_bytes"), py::arg("accumulate"), py::arg("device"),
+        py::arg("stream") = 0, py::arg("chunk") = 0);
+  // (points per lane, rows per workgroup tile) of the adjoint kernels for rows of n2 points
+  m.def("diffusion3d_adjoint_tile",
+        [](int64_t n2, int elem_bytes) {
+          if (elem_bytes != 4 && elem_bytes != 8) fail("diffusion3d_adjoint_tile: element size 4 or 8");
+          const AdjointTile t = diffusion3d_adjoint_tile(n2, elem_bytes);
+          return std::make_pair(t.vz, t.rows);
+        },
+        py::arg("n2"), py::arg("elem_bytes"));
   // Inner-box sweep through one restrict-form tiling id (fused_kernels.hip
   // dispatch_plain); the measurement-only tilings (incl. the timing probes
   // 130-132 of profiles/r2_refetch/refetch_probe.py) exist only in a --probes build.

@@ -154,6 +154,36 @@ void launch_diffusion3d_fused(const DiffusionArgs& a, const HaloIOArgs& io, int 
                               hipStream_t stream);
 void host_diffusion3d(const DiffusionArgs& a, const std::vector<Box>& boxes);
 
+// Transpose of the step (stencil_adj_kernels.hip, stencil_adj_host.cpp; the
+// point arithmetic: igg/stencil_adj.hpp). One call of the adjoint: gt != 0 asks for gT = S^T g (reads g and cp, or q
+// where q != 0), gcp != 0 for the derivative with respect to Cp (reads t, cp
+// and g; accumulate: added to gcp's interior cells, its boundary cells
+// untouched). All arrays are C-contiguous (n0, n1, n2), dim 2 fastest. An
+// array with an extent below 3 has no interior: gT = g and gCp = 0.
+struct DiffusionAdjointArgs {
+  uintptr_t gt = 0, gcp = 0;
+  uintptr_t g = 0, cp = 0, q = 0, t = 0;
+  int64_t n[3] = {0, 0, 0};
+  double rd2[3] = {0, 0, 0};
+  double dt_lam = 0;
+  int elem_bytes = 8;
+  bool accumulate = false;
+  int chunk = 0;  // planes per x chunk of a workgroup; 0: sized to the device
+};
+
+// Tiling of the kernels for rows of n2 points: points per lane (the 16-byte
+// vector where n2 is a multiple of it, else 1), rows per workgroup tile.
+struct AdjointTile {
+  int vz, rows;
+};
+AdjointTile diffusion3d_adjoint_tile(int64_t n2, int elem_bytes);
+
+// Both check the arguments first (check_diffusion3d_adjoint: what is asked
+// for has its inputs, no output aliases an input) and fail before any write.
+void check_diffusion3d_adjoint(const DiffusionAdjointArgs& a);
+void launch_diffusion3d_adjoint(const DiffusionAdjointArgs& a, hipStream_t stream);
+void host_diffusion3d_adjoint(const DiffusionAdjointArgs& a);
+
 // Boundary-slab / interior decomposition of the inner box [1,n-1)^3.
 // At every side with `active[d][side]`, a slab of width w[d] is split off (it
 // holds the plane that update_halo sends to that side). Returns {slabs, interior}.

@@ -25,7 +25,10 @@ them (parallel/accumulate.py), with the differentiable exchange
 ``igg.autograd.update_halo`` built on it; and ``sample_g``, the fields' values
 at arbitrary points of the global grid, interpolated by the rank that owns
 each point's cell, with ``Recorder`` for time series of them
-(``sample_owner``, ``index_g``; parallel/sample_g.py).
+(``sample_owner``, ``index_g``; parallel/sample_g.py); and the diffusion step
+transposed (``ops.stencil.diffusion3d_adjoint_``), with the differentiable step
+``igg.autograd.diffusion3d`` and the model's backward time loop
+``Diffusion3D.adjoint_run``.
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401

@@ -1,4 +1,4 @@
-"""Differentiable halo exchange.
+"""Differentiable halo exchange and diffusion step.
 
 ``update_halo_`` works in place and autograd does not see it.
 ``igg.autograd.update_halo(*fields)`` is the same exchange out of place, as a
@@ -7,11 +7,20 @@ the clones' halos, the backward pass applies the transpose of the exchange
 (``accumulate_halo_``) to the incoming gradients. One call covers all fields, so
 both passes group them in one exchange. Like ``update_halo_`` the call is
 collective: every rank runs the forward and the backward pass.
+
+``igg.autograd.diffusion3d(T, Cp, ...)`` is the other factor of a time step of
+``Diffusion3D``: the stencil update ``S(T)`` out of place (boundary cells keep
+``T``'s values), whose backward pass runs the adjoint kernels
+(``ops.stencil.diffusion3d_adjoint_``). ``update_halo(diffusion3d(T, Cp, ...))``
+is one differentiable step of the model on any number of ranks.
 """
 from __future__ import annotations
 
 import torch
 
+from torch.autograd.function import once_differentiable
+
+from .ops import stencil as _stencil
 from .parallel.accumulate import accumulate_halo_
 from .parallel.halo import update_halo_
 
@@ -40,3 +49,46 @@ def update_halo(*fields):
     of the rank they were copied from."""
     outs = _UpdateHalo.apply(*fields)
     return outs[0] if len(fields) == 1 else outs
+
+
+class _Diffusion3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, T, Cp, lam, dt, dx, dy, dz):
+        Td = T.detach().contiguous()
+        Cpd = Cp.detach().contiguous()
+        out = Td.clone(memory_format=torch.contiguous_format)  # boundary cells: T's
+        if Td.dim() != 3 or min(Td.shape) >= 3:  # (below 3 there is no interior: S is the identity)
+            _stencil.diffusion3d_(out, Td, Cpd, lam=lam, dt=dt, dx=dx, dy=dy, dz=dz)
+        ctx.kw = dict(lam=lam, dt=dt, dx=dx, dy=dy, dz=dz)
+        # the transpose with respect to T needs no forward state (S is linear in T)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(Cpd, Td)
+        else:
+            ctx.save_for_backward(Cpd)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        Cp = ctx.saved_tensors[0]
+        g = gout.contiguous()
+        need_t, need_cp = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gT = torch.empty_like(g) if need_t else None
+        gCp = torch.empty_like(g) if need_cp else None
+        if need_t or need_cp:
+            _stencil.diffusion3d_adjoint_(gT, g, Cp, T=ctx.saved_tensors[1] if need_cp else None, gCp=gCp, **ctx.kw)
+        return gT, gCp, None, None, None, None, None
+
+
+def diffusion3d(T, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: float):
+    """One diffusion update of ``T`` as a new tensor; differentiable in ``T``
+    and ``Cp``.
+
+    The result is ``T + dt*lam/Cp * laplace(T)`` on interior cells, computed by
+    ``ops.stencil.diffusion3d_``, and ``T`` itself on boundary cells - the map
+    a step of ``Diffusion3D`` applies before its halo exchange. The backward
+    pass launches only the adjoint kernels that the inputs requiring a
+    gradient ask for (``ops.stencil.diffusion3d_adjoint_``); ``T`` is kept for
+    it only when ``Cp`` requires a gradient. CPU and GPU tensors, float32 and
+    float64, 3-D; ``lam``, ``dt`` and the spacings are plain numbers."""
+    return _Diffusion3D.apply(T, Cp, float(lam), float(dt), float(dx), float(dy), float(dz))

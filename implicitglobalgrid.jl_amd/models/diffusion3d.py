@@ -385,6 +385,72 @@ class Diffusion3D(PingPongModel):
     run.__doc__ = PingPongModel.run.__doc__
     capture.__doc__ = PingPongModel.capture.__doc__
 
+    def _q_current(self) -> bool:
+        """``Q`` exists and was built from ``Cp``, ``dt`` and ``lam`` as they are."""
+        return self.Q is not None and self._q_key == (self.Cp.data_ptr(), self.Cp._version, self.dt * self.lam)
+
+    def adjoint_run(self, nt: int, g, out=None):
+        """The transpose of ``run(nt)`` applied to ``g``: the gradient of
+        ``<g, T after nt steps>`` with respect to the LOCAL array ``T`` that
+        the steps started from.
+
+        ``g`` has the shape, dtype and device of ``T`` and is not modified;
+        the result is a new tensor, or ``out``. A step of the model is
+        ``T <- H(S(T))`` - the stencil update ``S``, then ``update_halo_``
+        (``H``) - so each of the ``nt`` adjoint steps is
+        ``accumulate_halo_(g)`` (``Hᵀ``) followed by ``g' = Sᵀ g``
+        (``ops.stencil.diffusion3d_adjoint_``), on two ping-pong buffers. ``S``
+        is linear in ``T``: no forward state is stored or needed. ``run``
+        leaves bitwise the values of single steps whichever pass it took, so
+        this is the adjoint of ``run(nt)`` on every grid the model accepts. It
+        uses the model's ``lam``, ``dt``, spacings and ``Cp``, and ``Q`` where
+        the model keeps one that is current; it touches neither ``T`` and
+        ``T2`` nor a captured graph. Collective like ``run``; it raises where
+        ``accumulate_halo_`` would (a field with ``n < overlap + halowidth``
+        in an exchanging dimension).
+
+        The result is the gradient with respect to the LOCAL array: halo cells
+        hold the part that belongs to the cell's owner on another rank. Where
+        ``overlap == 2*halowidth`` in every exchanging dimension (the default
+        grid), every cell a rank does not own is a halo cell, and one more
+        ``accumulate_halo_(result)`` leaves the gradient with respect to the
+        GLOBAL initial field in the owned cells (``gather_g`` assembles it).
+        Wider overlaps need the transpose of ``scatter_g`` for that."""
+        from ..parallel.accumulate import accumulate_halo_, check_accumulate
+
+        nt = int(nt)
+        if nt < 0:
+            raise IGGError("adjoint_run: nt must be >= 0")
+        for name, A in (("g", g), ("out", out)):
+            if A is None:
+                continue
+            if not isinstance(A, torch.Tensor) or A.shape != self.T.shape or A.dtype != self.T.dtype \
+                    or A.device != self.T.device:
+                raise IGGError(f"adjoint_run: {name} must have T's shape {tuple(self.T.shape)}, dtype {self.T.dtype} "
+                               f"and device {self.T.device}")
+            if not A.is_contiguous():
+                raise IGGError(f"adjoint_run: {name} must be C-contiguous")
+        check_accumulate(g)
+        if out is None:
+            a = g.clone(memory_format=torch.contiguous_format)
+        else:
+            a = out
+            if out.data_ptr() != g.data_ptr():
+                out.copy_(g)
+        if nt == 0:
+            return a
+        b = torch.empty_like(a)
+        Q = self.Q if self._q_current() else None
+        for _ in range(nt):
+            accumulate_halo_(a)
+            stencil.diffusion3d_adjoint_(b, a, self.Cp, Q=Q, lam=self.lam, dt=self.dt, dx=self.dx, dy=self.dy,
+                                         dz=self.dz)
+            a, b = b, a
+        if out is not None and a is not out:
+            out.copy_(a)
+            return out
+        return a
+
     def _swap(self) -> None:
         self.T, self.T2 = self.T2, self.T
 

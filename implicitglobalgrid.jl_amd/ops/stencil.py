@@ -435,6 +435,93 @@ def time_acoustic_twostep_pingpong(a, b, launch_single, launch_pass, chunks, ste
     return med.pop(None), med
 
 
+def _overlaps(A, B) -> bool:
+    """Whether the bytes of two dense tensors overlap (same device)."""
+    if A.device != B.device or A.numel() == 0 or B.numel() == 0:
+        return False
+    a0, b0 = A.data_ptr(), B.data_ptr()
+    return a0 < b0 + B.numel() * B.element_size() and b0 < a0 + A.numel() * A.element_size()
+
+
+def diffusion3d_adjoint_(gT, g, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: float,
+                         Q=None, T=None, gCp=None, accumulate: bool = False, stream: int | None = None,
+                         chunk: int = 0) -> None:
+    """The transpose of one diffusion step, applied to ``g``.
+
+    With ``S`` the step as the model's loop uses it - ``diffusion3d_`` on the
+    whole interior into an array whose boundary cells hold ``T``'s - this
+    writes ``gT = Sᵀ g`` (every cell of ``gT``, boundary cells included: they
+    are copied by ``S``, so they keep their own ``g`` and receive from their
+    interior neighbour, but send nothing through the stencil) and, where
+    ``gCp`` is given, the derivative with respect to ``Cp``,
+    ``gCp = -(dt*lam/Cp * g / Cp) * laplace(T)`` on interior cells and 0 on
+    boundary cells. ``S`` is linear in ``T``, so ``gT`` needs no forward
+    state; ``gCp`` needs the step's input ``T``.
+
+    ``gT=None`` skips the first kernel. ``Q``: the array ``quotient_`` left
+    for this ``Cp`` and ``dt*lam``; ``gT`` is then computed from it, ``Cp`` is
+    not read for it, and the values are bitwise the same. ``accumulate=True``
+    adds into ``gCp``'s interior cells and leaves its boundary cells alone.
+    Boundary values of ``Cp`` and ``Q`` reach no result (``Cp == 0`` there is
+    fine). An array with an extent below 3 has no interior: ``gT = g`` and
+    ``gCp = 0``.
+
+    CPU and GPU tensors, float32 / float64, 3-D and C-contiguous, all of one
+    shape, dtype and device. GPU work is ordered on ``stream`` (default: the
+    current stream) and can be captured in a hipGraph; the CPU path is the
+    threaded host twin, which gives bitwise what the kernels give. ``chunk``:
+    planes along x per workgroup (0: sized to the device). ``gT`` must not
+    overlap ``g`` (the kernel reads neighbours) and ``gCp`` no other
+    argument; every failed check raises ``IGGError`` before anything is
+    written."""
+    who = "diffusion3d_adjoint"
+    named = [("g", g), ("gT", gT), ("Cp", Cp), ("Q", Q), ("T", T), ("gCp", gCp)]
+    if g is None or Cp is None:
+        raise IGGError(f"{who}: g and Cp are required")
+    for name, A in named:
+        if A is None:
+            continue
+        if not isinstance(A, torch.Tensor) or A.dim() != 3:
+            raise IGGError(f"{who}: {name} must be a 3-D tensor")
+        if A.shape != g.shape:
+            raise IGGError(f"{who}: {name} has shape {tuple(A.shape)}, g has {tuple(g.shape)}")
+        if A.dtype != g.dtype:
+            raise IGGError(f"{who}: {name} has dtype {A.dtype}, g has {g.dtype}")
+        if A.device != g.device:
+            raise IGGError(f"{who}: {name} is on {A.device}, g is on {g.device}")
+        if not A.is_contiguous():
+            raise IGGError(f"{who}: {name} must be C-contiguous")
+    if g.dtype not in (torch.float32, torch.float64):
+        raise IGGError(f"{who}: g must be float32 or float64 (got {g.dtype})")
+    if gCp is not None and T is None:
+        raise IGGError(f"{who}: gCp needs T, the input of the forward step")
+    if gT is not None and _overlaps(gT, g):
+        raise IGGError(f"{who}: gT must not alias g (the kernel reads g's neighbours)")
+    if gT is not None:
+        for name, A in (("Cp", Cp), ("Q", Q), ("T", T)):
+            if A is not None and _overlaps(gT, A):
+                raise IGGError(f"{who}: gT must not alias {name}")
+    if gCp is not None:
+        for name, A in named[:5]:
+            if A is not None and _overlaps(gCp, A):
+                raise IGGError(f"{who}: gCp must not alias {name}")
+    if int(chunk) < 0:
+        raise IGGError(f"{who}: chunk must be >= 0")
+    if gT is None and gCp is None:
+        return
+    rd2 = [1.0 / (dx * dx), 1.0 / (dy * dy), 1.0 / (dz * dz)]
+    dev = g.is_cuda
+    s = 0
+    if dev:
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+
+    def ptr(A):
+        return 0 if A is None else A.data_ptr()
+
+    native.diffusion3d_adjoint(ptr(gT), ptr(gCp), ptr(g), ptr(Cp), ptr(Q), ptr(T), list(g.shape), rd2, dt * lam,
+                               g.element_size(), bool(accumulate), dev, s, int(chunk))
+
+
 def diffusion3d_reference(T, Cp, *, lam, dt, dx, dy, dz) -> torch.Tensor:
     """Plain-PyTorch (fp64) reference of the reference example's 5 broadcasts."""
     T = T.double()

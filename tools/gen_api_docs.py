@@ -32,7 +32,9 @@ SECTIONS = [
     ("Halo engine knobs", "igg.parallel.halo",
      ["set_transport", "transport_name", "tuned_transports", "set_halo_mode", "halo_mode", "set_pack_mode",
       "pack_mode", "enable_loopback", "sendranges", "recvranges", "halosize", "free_update_halo_buffers"]),
-    ("Stencil ops", "igg.ops.stencil", ["diffusion3d_", "diffusion3d_reference", "time_variants", "autotune"]),
+    ("Stencil ops", "igg.ops.stencil",
+     ["diffusion3d_", "diffusion3d_adjoint_", "diffusion3d_reference", "time_variants", "autotune"]),
+    ("Differentiable operators", "igg.autograd", ["update_halo", "diffusion3d"]),
     ("Applications", "igg.models.diffusion3d", ["Diffusion3D"]),
     ("", "igg.models.acoustic2d", ["Acoustic2D"]),
     ("Field placement", "igg.utils.placement", ["candidate_count", "time_candidates", "placed"]),
