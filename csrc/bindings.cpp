@@ -1136,6 +1136,29 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("nx"), py::arg("ny"), py::arg("elem_bytes"));
   m.def("acoustic2d_set_variant", &acoustic2d_set_variant);
   m.def("acoustic2d_set_chunk", &acoustic2d_set_chunk);
+  // Transpose of the step (acoustic_adj_kernels.hip / acoustic_adj_host.cpp):
+  // (gP2, gVx2, gVy2) -> (gP, gVx, gVy).
+  m.def("acoustic2d_adjoint",
+        [](uintptr_t gp, uintptr_t gvx, uintptr_t gvy, uintptr_t gp2, uintptr_t gvx2, uintptr_t gvy2, int64_t nx,
+           int64_t ny, double dtk, double dt_rho, double rdx, double rdy, int elem_bytes, bool device,
+           uintptr_t stream, int64_t chunk) {
+          TraceRange tr("igg.acoustic2d_adjoint");
+          AcousticAdjointArgs a{gp, gvx, gvy, gp2, gvx2, gvy2, nx, ny, dtk, dt_rho, rdx, rdy, elem_bytes, chunk};
+          if (device) {
+            launch_acoustic2d_adjoint(a, as_stream(stream));
+          } else {
+            check_acoustic2d_adjoint(a);
+            py::gil_scoped_release nogil;
+            host_acoustic2d_adjoint(a);
+          }
+        },
+        py::arg("gp"), py::arg("gvx"), py::arg("gvy"), py::arg("gp2"), py::arg("gvx2"), py::arg("gvy2"),
+        py::arg("nx"), py::arg("ny"), py::arg("dtk"), py::arg("dt_rho"), py::arg("rdx"), py::arg("rdy"),
+        py::arg("elem_bytes"), py::arg("device"), py::arg("stream") = 0, py::arg("chunk") = 0);
+  m.def("acoustic2d_adjoint_set_chunk", &acoustic2d_adjoint_set_chunk, py::arg("rows"),
+        "Rows of x per wave of the adjoint acoustic kernel where a call passes chunk = 0 (0: the built-in default).");
+  m.def("acoustic2d_adjoint_chunk", &acoustic2d_adjoint_chunk,
+        "Rows of x per wave that a call with chunk = 0 gets.");
   m.def("diffusion3d_set_rounds", &diffusion3d_set_rounds);
   m.def("diffusion3d_get_rounds", &diffusion3d_get_rounds);
   m.def("diffusion3d",

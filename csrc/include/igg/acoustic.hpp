@@ -75,6 +75,28 @@ void launch_acoustic2d_twostep(const AcousticArgs& a, int64_t chunk, hipStream_t
 // 16-byte vector (VJ = 4 / 2) and >= 2 * VJ, nx >= 1.
 bool acoustic2d_twostep_ok(const AcousticArgs& a);
 
+// Transpose of one step (kernels/acoustic_adj_kernels.hip, acoustic_adj_host.cpp;
+// point arithmetic: igg/acoustic_adj.hpp): (gP2, gVx2, gVy2) -> (gP, gVx, gVy),
+// shapes and coefficients as in AcousticArgs. The step is linear, so no
+// forward state is needed. Every element of the outputs is written and the
+// inputs are only read; one kernel, three arrays read and three written.
+struct AcousticAdjointArgs {
+  uintptr_t gp, gvx, gvy;     // outputs: gradient with respect to P, Vx, Vy
+  uintptr_t gp2, gvx2, gvy2;  // inputs: gradient with respect to P2, Vx2, Vy2
+  int64_t nx, ny;
+  double dtk, dt_rho;
+  double rdx, rdy;
+  int elem_bytes;
+  int64_t chunk = 0;          // rows of i per wave (0: acoustic2d_adjoint_set_chunk's value, or the default)
+};
+// Both check the arguments first (check_acoustic2d_adjoint: extents, element
+// size, null or equal pointers, chunk) and fail before anything is written.
+void check_acoustic2d_adjoint(const AcousticAdjointArgs& a);
+void launch_acoustic2d_adjoint(const AcousticAdjointArgs& a, hipStream_t stream);
+void host_acoustic2d_adjoint(const AcousticAdjointArgs& a);
+void acoustic2d_adjoint_set_chunk(int64_t rows);  // process default of `chunk` (0: the built-in one)
+int64_t acoustic2d_adjoint_chunk();               // the rows per wave a call with chunk = 0 gets
+
 // Fused halo exchange of Acoustic2D, the counterpart of FusedHalo (fused.hpp)
 // for the 2-D staggered step. update_halo!(Vx2, Vy2) (reference semantics,
 // src/update_halo.jl:32-78) would overwrite Vx2's x-halo faces and y-halo

@@ -28,7 +28,9 @@ each point's cell, with ``Recorder`` for time series of them
 (``sample_owner``, ``index_g``; parallel/sample_g.py); and the diffusion step
 transposed (``ops.stencil.diffusion3d_adjoint_``), with the differentiable step
 ``igg.autograd.diffusion3d`` and the model's backward time loop
-``Diffusion3D.adjoint_run``.
+``Diffusion3D.adjoint_run``; and the acoustic step transposed
+(``ops.stencil.acoustic2d_adjoint_``), with ``igg.autograd.acoustic2d`` and
+``Acoustic2D.adjoint_run``.
 """
 from ._native import IGGError, PROC_NULL, native, native_path  # noqa: F401
 from .parallel.grid import (  # noqa: F401

@@ -1,4 +1,4 @@
-"""Differentiable halo exchange and diffusion step.
+"""Differentiable halo exchange, diffusion step and acoustic step.
 
 ``update_halo_`` works in place and autograd does not see it.
 ``igg.autograd.update_halo(*fields)`` is the same exchange out of place, as a
@@ -13,6 +13,12 @@ collective: every rank runs the forward and the backward pass.
 ``T``'s values), whose backward pass runs the adjoint kernels
 (``ops.stencil.diffusion3d_adjoint_``). ``update_halo(diffusion3d(T, Cp, ...))``
 is one differentiable step of the model on any number of ranks.
+
+``igg.autograd.acoustic2d(P, Vx, Vy, ...)`` is the staggered update of
+``Acoustic2D`` out of place, ``(P2, Vx2, Vy2)``; its backward pass is one launch
+of the adjoint kernel (``ops.stencil.acoustic2d_adjoint_``). The step is linear,
+so nothing is saved. ``update_halo(Vx2, Vy2)`` after it makes one differentiable
+step of that model on any number of ranks (``P2`` is never exchanged).
 """
 from __future__ import annotations
 
@@ -92,3 +98,37 @@ def diffusion3d(T, Cp, *, lam: float, dt: float, dx: float, dy: float, dz: float
     it only when ``Cp`` requires a gradient. CPU and GPU tensors, float32 and
     float64, 3-D; ``lam``, ``dt`` and the spacings are plain numbers."""
     return _Diffusion3D.apply(T, Cp, float(lam), float(dt), float(dx), float(dy), float(dz))
+
+
+class _Acoustic2D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, Vx, Vy, dt, K, rho, dx, dy):
+        ins = [A.detach().contiguous() for A in (P, Vx, Vy)]
+        outs = [torch.empty_like(A) for A in ins]
+        _stencil._acoustic_step(*outs, *ins, dt=dt, K=K, rho=rho, dx=dx, dy=dy)
+        ctx.kw = dict(dt=dt, K=K, rho=rho, dx=dx, dy=dy)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gP2, gVx2, gVy2):
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * 8
+        gin = [g.contiguous() for g in (gP2, gVx2, gVy2)]
+        gout = [torch.empty_like(g) for g in gin]
+        _stencil.acoustic2d_adjoint_(*gout, *gin, **ctx.kw)
+        return tuple(g if need else None for g, need in zip(gout, ctx.needs_input_grad[:3])) + (None,) * 5
+
+
+def acoustic2d(P, Vx, Vy, *, dt: float, K: float, rho: float, dx: float, dy: float):
+    """One staggered acoustic update as new tensors ``(P2, Vx2, Vy2)``;
+    differentiable in ``P``, ``Vx`` and ``Vy``.
+
+    The forward pass is the step of ``Acoustic2D`` before its halo exchange
+    (``P`` (nx, ny), ``Vx`` (nx+1, ny), ``Vy`` (nx, ny+1); the boundary faces
+    of ``Vx``/``Vy`` are copied). The backward pass is one launch of the
+    adjoint kernel (``ops.stencil.acoustic2d_adjoint_``); the step is linear,
+    so no forward state is kept, and an input that needs no gradient gets
+    ``None``. CPU and GPU tensors, float32 and float64; ``dt``, ``K``, ``rho``
+    and the spacings are plain numbers (no gradient flows to them)."""
+    return _Acoustic2D.apply(P, Vx, Vy, float(dt), float(K), float(rho), float(dx), float(dy))

@@ -35,7 +35,7 @@ import os
 import torch
 
 from .. import parallel  # noqa: F401
-from .._native import native
+from .._native import IGGError, native
 from ..ops import stencil as _stencil
 from ..parallel import grid as _grid
 from ..parallel.halo import update_halo_
@@ -260,6 +260,80 @@ class Acoustic2D(PingPongModel):
         the update_halo_ path only from states where those copies agree."""
         self._update(self.P2, self.Vx2, self.Vy2, self.P, self.Vx, self.Vy)
         self._swap()
+
+    def adjoint_run(self, nt: int, gP, gVx, gVy, out=None):
+        """The transpose of ``run(nt)`` applied to ``(gP, gVx, gVy)``: the
+        gradient of ``<gP, P> + <gVx, Vx> + <gVy, Vy>``, taken after ``nt``
+        steps, with respect to the LOCAL arrays ``P``, ``Vx``, ``Vy`` that the
+        steps started from. Returns ``(gP, gVx, gVy)`` as new tensors, or the
+        three tensors of ``out``.
+
+        The arguments have the shape, dtype and device of ``P``, ``Vx`` and
+        ``Vy`` and are not modified. A step of the model is the staggered
+        update ``S``, then ``update_halo_(Vx2, Vy2)`` (``H``), so each of the
+        ``nt`` adjoint steps is ``accumulate_halo_(gVx, gVy)`` (``Hᵀ``)
+        followed by ``Sᵀ`` (``ops.stencil.acoustic2d_adjoint_``), on two sets of
+        ping-pong buffers; ``gP`` is never exchanged. ``S`` is linear: no
+        forward state is stored or needed. The fused step and the two-step
+        pass leave bitwise the values of single steps, so this is the adjoint
+        of ``run(nt)`` on every grid the model accepts. It uses the model's
+        ``dt``, ``K``, ``rho``, ``dx`` and ``dy`` as they are at the call and
+        touches neither the model's six fields nor a captured graph.
+        Collective like ``run``; it raises where ``accumulate_halo_`` would (a
+        field with ``n < overlap + halowidth`` in an exchanging dimension, the
+        loopback emulation).
+
+        The result is the gradient with respect to the LOCAL arrays: cells a
+        rank does not own hold the part that belongs to the cell's owner. For
+        ``P`` on the default grid (``overlap == 2*halowidth``) every such cell
+        is a halo cell, and one ``accumulate_halo_(gP)`` leaves the gradient
+        with respect to the GLOBAL initial pressure in the owned cells
+        (``gather_g`` assembles it). ``Vx`` and ``Vy`` have overlap 3 along
+        their staggered dimension, so one copy of a face is neither owned nor
+        halo: summing all copies of those fields needs the transpose of
+        ``scatter_g``, which does not exist yet."""
+        from ..parallel.accumulate import accumulate_halo_, check_accumulate
+
+        nt = int(nt)
+        if nt < 0:
+            raise IGGError("adjoint_run: nt must be >= 0")
+        like = (("P", self.P), ("Vx", self.Vx), ("Vy", self.Vy))
+        gs = (gP, gVx, gVy)
+        if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
+            raise IGGError("adjoint_run: out must be three tensors (gP, gVx, gVy)")
+        for what, arrs in (("g", gs), ("out ", out)):
+            if arrs is None:
+                continue
+            for (name, F), A in zip(like, arrs):
+                if not isinstance(A, torch.Tensor) or A.shape != F.shape or A.dtype != F.dtype or A.device != F.device:
+                    raise IGGError(f"adjoint_run: {what}{name} must have {name}'s shape {tuple(F.shape)}, dtype "
+                                   f"{F.dtype} and device {F.device}")
+                if not A.is_contiguous():
+                    raise IGGError(f"adjoint_run: {what}{name} must be C-contiguous")
+        if out is not None:
+            for k, A in enumerate(out):
+                if any(_stencil._overlaps(A, B) for B in tuple(out[k + 1:]) + tuple(g for j, g in enumerate(gs) if j != k)):
+                    raise IGGError("adjoint_run: a tensor of out overlaps another one or another field's g")
+        check_accumulate(gVx, gVy)
+        if out is None:
+            a = [g.clone(memory_format=torch.contiguous_format) for g in gs]
+        else:
+            a = list(out)
+            for o, g in zip(a, gs):
+                if o.data_ptr() != g.data_ptr():
+                    o.copy_(g)
+        if nt == 0:
+            return tuple(a)
+        b = [torch.empty_like(t) for t in a]
+        for _ in range(nt):
+            accumulate_halo_(a[1], a[2])
+            _stencil.acoustic2d_adjoint_(*b, *a, dt=self.dt, K=self.K, rho=self.rho, dx=self.dx, dy=self.dy)
+            a, b = b, a
+        if out is not None and a[0] is not out[0]:
+            for o, t in zip(out, a):
+                o.copy_(t)
+            return tuple(out)
+        return tuple(a)
 
     def _capture_start(self) -> None:
         if not self._warm or (self.fused and self._entry):

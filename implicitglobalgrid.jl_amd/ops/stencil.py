@@ -522,6 +522,89 @@ def diffusion3d_adjoint_(gT, g, Cp, *, lam: float, dt: float, dx: float, dy: flo
                                g.element_size(), bool(accumulate), dev, s, int(chunk))
 
 
+def _acoustic_step(P2, Vx2, Vy2, P, Vx, Vy, *, dt, K, rho, dx, dy) -> None:
+    """The single acoustic step on checked, dense tensors (igg.autograd.acoustic2d's
+    forward pass): the model's kernel, or its host twin, on the current stream."""
+    fields = (P2, Vx2, Vy2, P, Vx, Vy)
+    if not (_acoustic_shapes_ok(P, Vx, Vy) and _acoustic_shapes_ok(P2, Vx2, Vy2) and P2.shape == P.shape):
+        raise IGGError("acoustic2d: shapes must be P (nx, ny), Vx (nx+1, ny), Vy (nx, ny+1) "
+                       f"(got {[tuple(A.shape) for A in fields[3:]]})")
+    if P.numel() == 0:
+        raise IGGError("acoustic2d: needs nx >= 1 and ny >= 1")
+    if P.dtype not in (torch.float32, torch.float64):
+        raise IGGError(f"acoustic2d: the fields must be float32 or float64 (got {P.dtype})")
+    if any(A.dtype != P.dtype or A.device != P.device or not A.is_contiguous() for A in fields):
+        raise IGGError("acoustic2d: the fields must be C-contiguous and of one dtype and device")
+    dev = P.is_cuda
+    s = torch.cuda.current_stream().cuda_stream if dev else 0
+    native.acoustic2d(*(A.data_ptr() for A in fields), int(P.shape[0]), int(P.shape[1]), dt * K, dt / rho, 1.0 / dx,
+                      1.0 / dy, P.element_size(), dev, s)
+
+
+def acoustic2d_adjoint_(gP, gVx, gVy, gP2, gVx2, gVy2, *, dt: float, K: float, rho: float, dx: float, dy: float,
+                        chunk: int = 0, stream: int | None = None) -> None:
+    """The transpose of one acoustic step, applied to ``(gP2, gVx2, gVy2)``.
+
+    With ``S`` the staggered step ``(P, Vx, Vy) -> (P2, Vx2, Vy2)`` of
+    ``Acoustic2D`` (boundary faces of ``Vx``/``Vy`` copied), this writes
+    ``(gP, gVx, gVy) = Sᵀ (gP2, gVx2, gVy2)``, every element of the three
+    outputs. With ``a = dt*K``, ``b = dt/rho``::
+
+        wx = (b*gVx2)/dx on x-faces 1..nx-1, wy = (b*gVy2)/dy on y-faces 1..ny-1, else 0
+        r  = gP2 + ((wx[i+1]-wx[i]) + (wy[j+1]-wy[j]))
+        gP = r,  gVx = gVx2 + (a*(r[i]-r[i-1]))/dx,  gVy = gVy2 + (a*(r[j]-r[j-1]))/dy
+
+    with ``r = 0`` outside the cells. ``S`` is linear, so no forward state is
+    needed. Zeros are selected, never multiplied: what a boundary face of
+    ``gVx2``/``gVy2`` holds (NaN, Inf) reaches that face of ``gVx``/``gVy`` and
+    nothing else.
+
+    Shapes as in the step: ``gP``/``gP2`` (nx, ny), ``gVx``/``gVx2``
+    (nx+1, ny), ``gVy``/``gVy2`` (nx, ny+1), ``nx, ny >= 1``; CPU and GPU
+    tensors, float32 / float64, C-contiguous, all of one dtype and device. GPU
+    work is one kernel (csrc/kernels/acoustic_adj_kernels.hip: three arrays
+    read, three written) ordered on ``stream`` (default: the current stream)
+    and can be captured in a hipGraph; the CPU path is the threaded host twin,
+    which gives bitwise what the kernel gives. ``chunk``: rows of x per wave
+    (0: the kernel's default). No output may overlap an input or another
+    output; every failed check raises ``IGGError`` before anything is
+    written."""
+    who = "acoustic2d_adjoint"
+    outs = (("gP", gP), ("gVx", gVx), ("gVy", gVy))
+    ins = (("gP2", gP2), ("gVx2", gVx2), ("gVy2", gVy2))
+    for name, A in outs + ins:
+        if not isinstance(A, torch.Tensor) or A.dim() != 2:
+            raise IGGError(f"{who}: {name} must be a 2-D tensor")
+    if not (_acoustic_shapes_ok(gP2, gVx2, gVy2) and _acoustic_shapes_ok(gP, gVx, gVy) and gP.shape == gP2.shape):
+        raise IGGError(f"{who}: shapes must be gP (nx, ny), gVx (nx+1, ny), gVy (nx, ny+1), inputs and outputs "
+                       f"alike (got {[tuple(A.shape) for _n, A in outs + ins]})")
+    nx, ny = int(gP2.shape[0]), int(gP2.shape[1])
+    if nx < 1 or ny < 1:
+        raise IGGError(f"{who}: needs nx >= 1 and ny >= 1 (got {nx} x {ny})")
+    for name, A in outs + ins:
+        if A.dtype != gP2.dtype:
+            raise IGGError(f"{who}: {name} has dtype {A.dtype}, gP2 has {gP2.dtype}")
+        if A.device != gP2.device:
+            raise IGGError(f"{who}: {name} is on {A.device}, gP2 is on {gP2.device}")
+        if not A.is_contiguous():
+            raise IGGError(f"{who}: {name} must be C-contiguous")
+    if gP2.dtype not in (torch.float32, torch.float64):
+        raise IGGError(f"{who}: the fields must be float32 or float64 (got {gP2.dtype})")
+    for k, (name, A) in enumerate(outs):
+        for other, B in outs[k + 1:] + ins:
+            if _overlaps(A, B):
+                raise IGGError(f"{who}: {name} must not overlap {other}")
+    if int(chunk) < 0:
+        raise IGGError(f"{who}: chunk must be >= 0")
+    dev = gP2.is_cuda
+    s = 0
+    if dev:
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    native.acoustic2d_adjoint(gP.data_ptr(), gVx.data_ptr(), gVy.data_ptr(), gP2.data_ptr(), gVx2.data_ptr(),
+                              gVy2.data_ptr(), nx, ny, dt * K, dt / rho, 1.0 / dx, 1.0 / dy, gP2.element_size(),
+                              dev, s, int(chunk))
+
+
 def diffusion3d_reference(T, Cp, *, lam, dt, dx, dy, dz) -> torch.Tensor:
     """Plain-PyTorch (fp64) reference of the reference example's 5 broadcasts."""
     T = T.double()

@@ -33,8 +33,9 @@ SECTIONS = [
      ["set_transport", "transport_name", "tuned_transports", "set_halo_mode", "halo_mode", "set_pack_mode",
       "pack_mode", "enable_loopback", "sendranges", "recvranges", "halosize", "free_update_halo_buffers"]),
     ("Stencil ops", "igg.ops.stencil",
-     ["diffusion3d_", "diffusion3d_adjoint_", "diffusion3d_reference", "time_variants", "autotune"]),
-    ("Differentiable operators", "igg.autograd", ["update_halo", "diffusion3d"]),
+     ["diffusion3d_", "diffusion3d_adjoint_", "acoustic2d_adjoint_", "diffusion3d_reference", "time_variants",
+      "autotune"]),
+    ("Differentiable operators", "igg.autograd", ["update_halo", "diffusion3d", "acoustic2d"]),
     ("Applications", "igg.models.diffusion3d", ["Diffusion3D"]),
     ("", "igg.models.acoustic2d", ["Acoustic2D"]),
     ("Field placement", "igg.utils.placement", ["candidate_count", "time_candidates", "placed"]),
