@@ -33,6 +33,7 @@
 #include "igg/topology.hpp"
 #include "igg/trace.hpp"
 #include "igg/vmm.hpp"
+#include "igg/zedge.hpp"
 
 namespace igg {
 void launch_zcol_probe(int dir, const void* src, void* dst, int64_t rows, int64_t pitch, int aux,
@@ -1289,6 +1290,26 @@ PYBIND11_MODULE(_igg_native, m) {
     return v;
   });
   m.def("diffusion3d_fused_variant_ok", &diffusion3d_fused_variant_ok);
+  // (BY, RY, VZ, BZ, dpp) of a compiled fused variant: host arithmetic
+  m.def("diffusion3d_fused_tile",
+        [](int v) {
+          const FusedTile t = diffusion3d_fused_tile(v);
+          return std::make_tuple(t.by, t.ry, t.vz, t.bz, t.dpp);
+        },
+        py::arg("variant"));
+  // The z-edge lane rule of the fused kernels (igg/zedge.hpp), as the kernel
+  // evaluates it: (lo, hi, rl, rh, src, src_row, dst, dst_row) of one lane.
+  m.def("fused_zedge_lane",
+        [](bool dpp, int lane, int zh, int nv, bool in_lo, bool in_hi, bool out_lo, bool out_hi) {
+          const ZEdgeLane z = zedge_lane(dpp, lane, zh, nv, in_lo, in_hi, out_lo, out_hi);
+          return std::make_tuple(z.lo, z.hi, z.rl, z.rh, z.src, z.src_row, z.dst, z.dst_row);
+        },
+        py::arg("dpp"), py::arg("lane"), py::arg("zh"), py::arg("nv"), py::arg("in_lo"), py::arg("in_hi"),
+        py::arg("out_lo"), py::arg("out_hi"));
+  m.def("fused_zedge_zh", &zedge_zh, py::arg("n2"), py::arg("vz"));
+  m.def("fused_zedge_one_wave", &zedge_one_wave, py::arg("n2"), py::arg("vz"));
+  m.def("fused_zedge_dpp_rows_fit", &zedge_dpp_rows_fit, py::arg("zh"), py::arg("ry"));
+  m.def("fused_zedge_dpp_ok", &zedge_dpp_ok, py::arg("n2"), py::arg("vz"), py::arg("ry"));
   m.def("diffusion3d_variant_compiled", &stencil_variant_compiled,
         "Whether stencil variant v is compiled in this build (measurement-only ones: build.py --probes).");
   m.def("probes_build", []() {

@@ -30,6 +30,7 @@
 #include "igg/stencil.hpp"
 #include "igg/sysstore.hpp"
 #include "igg/vsweep.hpp"
+#include "igg/zedge.hpp"
 
 
 namespace igg {
@@ -38,6 +39,10 @@ namespace igg {
 // (defined in fused_kernels.hip).
 extern int64_t* g_hx_stamps;
 extern int g_hx_force_sel;
+// Set by diffusion3d_fused_tile() around a call of the families: launch_mode
+// writes its tiling there instead of launching (the template arguments in
+// igg/fused_families.hpp stay the only place that names a variant's tiling).
+extern FusedTile* g_hx_tile_query;
 
 // Fused launches by tiling family and element type, one translation unit each
 // so they compile in parallel (the tiling-9 family with its side-only z forms
@@ -359,7 +364,12 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   const T* zsrc = lo_l && zin_lo ? zi0 + (y0 - 1) + rl
                                  : (hi_l && zin_hi ? zi1 + (y0 - 1) + rh
                                                    : (zin_lo ? zi0 : zi1) + (y0 - 1));
-  const int64_t zro = ((y0 - 1) + (hi_l && !lo_l ? rh : rl)) * a.zrow;
+  // The row of the side zdst picks (igg/zedge.hpp): a ZDPP lane can hold row rl
+  // of the low edge and another row, rh, of the high edge. The readlane forms
+  // (rh == rl there) keep their expression to the letter: their register
+  // allocation moved with any rewording (profiles/fused_z_edges/NOTES.md).
+  const int64_t zro =
+      ((y0 - 1) + (ZD ? zedge_row(zedge_side(lo_l, hi_l, zout_lo, zout_hi), rl, rh) : (hi_l && !lo_l ? rh : rl))) * a.zrow;
   T* zdst = lo_l && zout_lo ? zo0 + zro : (hi_l && zout_hi ? zo1 + zro : nullptr);
   const bool remote = zout || yrow0 || yrow1 || (xs == 1 && xo0) || (xe == n0 - 1 && xo1);
   T znext = T(0), zv = T(0);
@@ -972,18 +982,21 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
 // XF: extra FEAT bits of the tiling (512 | 1024 for fused variant 40).
 template <typename T, int BY, int RY, int VZ, bool PF, int BZ, int XF = 0>
 void launch_mode(const DiffusionArgs& d, const HaloIOArgs& io, int mode, hipStream_t s) {
+  if (g_hx_tile_query) {  // diffusion3d_fused_tile: report the tiling, launch nothing
+    *g_hx_tile_query = FusedTile{BY, RY, VZ, BZ, (XF & ZDPP) != 0};
+    return;
+  }
   if constexpr ((XF & ZDPP) != 0) {
     // the DPP z form: one z edge per wave, and the high edge's rows (lanes
     // zh - r) inside the edge lane's 16-lane DPP row
-    const int64_t zh = ((d.n[2] - VZ) % (64 * VZ)) / VZ;
-    if (d.n[2] <= 64 * VZ + VZ || zh % 16 < RY - 1) {
+    if (!zedge_dpp_ok(d.n[2], VZ, RY)) {
       launch_mode<T, BY, RY, VZ, PF, BZ, (XF & ~ZDPP)>(d, io, mode, s);
       return;
     }
   }
   if constexpr ((XF & 8192) != 0) {
     // the edge-lane z form needs every wave to hold at most one z edge
-    if (d.n[2] <= 64 * VZ + VZ) {
+    if (zedge_one_wave(d.n[2], VZ)) {
       launch_mode<T, BY, RY, VZ, PF, BZ, (XF & ~8192)>(d, io, mode, s);
       return;
     }

@@ -139,6 +139,14 @@ struct HaloIOArgs {
   bool* sync_used = nullptr;
 };
 bool diffusion3d_fused_variant_ok(int v);
+// Tiling of fused variant v: a workgroup of by x bz waves, each wave ry rows of
+// 64 vectors of vz points; dpp: the z edge moves as DPP row shifts where the
+// shape admits it (igg/zedge.hpp zedge_dpp_ok). Host arithmetic, no launch.
+struct FusedTile {
+  int by, ry, vz, bz;
+  bool dpp;
+};
+FusedTile diffusion3d_fused_tile(int v);
 // Diagnostics of the fused kernel: per-wave {feature class, start, end, hw id}
 // stamps (4 x int64 per wave, wall_clock64 ticks) into device memory `stamps`
 // (nullptr: off), and force_sel >= 0 runs every wave with that feature class

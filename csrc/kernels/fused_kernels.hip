@@ -8,6 +8,7 @@ namespace igg {
 
 int64_t* g_hx_stamps = nullptr;
 int g_hx_force_sel = -1;
+FusedTile* g_hx_tile_query = nullptr;
 
 namespace {
 
@@ -95,6 +96,19 @@ bool diffusion3d_fused_variant_ok(int v) {
   if (v == 2 || v == 11 || v == 41 || v == 45) return true;
 #endif
   return v == 0 || v == 9 || v == 14 || v == 40 || v == 42 || v == 44 || v == 48 || v == 50;
+}
+
+FusedTile diffusion3d_fused_tile(int v) {
+  if (!diffusion3d_fused_variant_ok(v)) fail("diffusion3d (fused halo): variant ", v, " has no fused instantiation");
+  FusedTile t{};
+  const DiffusionArgs a{0, 0, 0, {3, 3, 8}, {1.0, 1.0, 1.0}, 0.0, 8};
+  const HaloIOArgs io{};
+  g_hx_tile_query = &t;  // launch_mode reports its template arguments and returns
+  const bool ok = fused_family_t0<double>(a, io, v, 0, nullptr) || fused_family_t11<double>(a, io, v, 0, nullptr) ||
+                  fused_family_t9<double>(a, io, v, 0, nullptr) || fused_family_t14<double>(a, io, v, 0, nullptr);
+  g_hx_tile_query = nullptr;
+  if (!ok) fail("diffusion3d (fused halo): variant ", v, " has no fused instantiation");
+  return t;
 }
 
 void launch_diffusion3d_fused(const DiffusionArgs& a, const HaloIOArgs& io, int variant, int mode,

@@ -196,7 +196,10 @@ def test_fused_dpp_z_matches_update_halo(gpu, mode, n2, periods):
     ZDPP): n2 = 320 / 512 put the high edge's rows inside the edge lane's
     16-lane row (zh = 15 / 63), so the DPP form runs; bitwise equal to
     stencil + update_halo_ in every send form (incl. z unpack and the
-    in-kernel step sync)."""
+    in-kernel step sync). Covers the send forms and period sets at those two
+    zh only, where no lane holds a row of both edges; the other lane positions
+    (zh = 7..15 and 16k + 7, the readlane fall-backs next to them, partial y
+    tiles) are swept in tests/test_gpu_fused_z_edges.py."""
     a, b = _pair((20, 26, n2), periods, torch.float64, 48, mode=mode)
     a.run(7)
     b.run(7)

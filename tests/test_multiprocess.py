@@ -264,7 +264,13 @@ SLOW = pytest.mark.slow  # redundant cases: IGG_TEST_SLOW=1 (conftest.py)
                                                # z unpack (mode bit 64) on 2x2x2 corner ranks and periodic
                                                (8, (18, 20, 136, 5, 0, 0), ("9", "72")),
                                                (8, (16, 18, 24, 6, 1, 1), ("42", "73")),
-                                               (2, (24, 20, 64, 6, 0, 1), ("0", "64"))])
+                                               (2, (24, 20, 64, 6, 0, 1), ("0", "64")),
+                                               # like the tiling-9 corner row above, for variant 48's DPP z
+                                               # form with the high edge at lane zh = 8 of the second wave: a
+                                               # wave that sends high only, its rows in lanes zh - r, into
+                                               # another rank's arena (tests/test_gpu_fused_z_edges.py sweeps
+                                               # zh on one rank); last, so the rows above keep their ids
+                                               (8, (18, 20, 292, 5, 0, 0), ("48", "8"))])
 def test_diffusion_gpu_multirank_fused(nprocs, cfg, kernel):
     # ranks share one GPU on the test box: RCCL cannot, so sync_halo uses 'put'
     env = {**PUT_ENV, "IGG_PUT_TIMEOUT": "20", "IGG_TEST_VARIANT": kernel[0], "IGG_TEST_FUSED_MODE": kernel[1]}
