@@ -33,8 +33,8 @@ import torch  # noqa: E402
 
 import igg  # noqa: E402
 from igg._native import native  # noqa: E402
+from igg.ops.stencil import SHORTLIST  # noqa: E402
 
-PLAIN = (2, 11, 14, 21, 24, 26, 40, 43, 44)  # ops/stencil.py SHORTLIST
 ROUNDS = (1, 2, 3)
 # bench.py FUSED_CANDIDATES / FUSED_DIRECT / FUSED_DIRECT_F32 (+ peel bit 8)
 FUSED = ((0, 0, 3), (0, 1, 3), (0, 0, 1), (9, 0, 3), (14, 0, 3), (40, 0, 2), (42, 0, 2), (42, 1, 2), (50, 0, 2),
@@ -176,7 +176,7 @@ def main() -> int:
     compiled = set(v for v in range(len(native.diffusion3d_variants())) if native.diffusion3d_variant_compiled(v))
     forms = (False, True) if hz else (False,)
     pl = bench({f"plain v{v}/r{r}" + ("/hz" if f else ""): plain(v, r, f)
-                for v in PLAIN if v in compiled for r in ROUNDS for f in forms})
+                for v in SHORTLIST if v in compiled for r in ROUNDS for f in forms})
     best_plain = min(pl, key=pl.get)
     print(f"n={n}^3 {a.dtype}: best plain {best_plain} {pl[best_plain]:.4f} ms "
           f"({3 * n ** 3 * eb / pl[best_plain] / 1e6:.0f} GB/s)", flush=True)

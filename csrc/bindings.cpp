@@ -1208,8 +1208,8 @@ PYBIND11_MODULE(_igg_native, m) {
           return std::make_pair(t.vz, t.rows);
         },
         py::arg("n2"), py::arg("elem_bytes"));
-  // Inner-box sweep through one restrict-form tiling id (fused_kernels.hip
-  // dispatch_plain); the measurement-only tilings (incl. the timing probes
+  // Inner-box sweep through one restrict-form tiling id (igg/variants.hpp
+  // IGG_RESTRICT_TILINGS*); the measurement-only tilings (incl. the timing probes
   // 130-132 of profiles/r2_refetch/refetch_probe.py) exist only in a --probes build.
   m.def("diffusion3d_hx_tiling",
         [](uintptr_t t2, uintptr_t t, uintptr_t cp, const Int3& n, const std::array<double, 3>& rd2,
@@ -1290,6 +1290,8 @@ PYBIND11_MODULE(_igg_native, m) {
     return v;
   });
   m.def("diffusion3d_fused_variant_ok", &diffusion3d_fused_variant_ok);
+  m.def("diffusion3d_fused_variants", &diffusion3d_fused_variants,
+        "Every fused variant index of the catalogue, ascending, whether this build compiles it or not.");
   // (BY, RY, VZ, BZ, dpp) of a compiled fused variant: host arithmetic
   m.def("diffusion3d_fused_tile",
         [](int v) {

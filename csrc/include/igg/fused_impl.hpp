@@ -29,6 +29,7 @@
 #include "igg/devsync.hpp"
 #include "igg/stencil.hpp"
 #include "igg/sysstore.hpp"
+#include "igg/variants.hpp"
 #include "igg/vsweep.hpp"
 #include "igg/zedge.hpp"
 
@@ -39,26 +40,14 @@ namespace igg {
 // (defined in fused_kernels.hip).
 extern int64_t* g_hx_stamps;
 extern int g_hx_force_sel;
-// Set by diffusion3d_fused_tile() around a call of the families: launch_mode
-// writes its tiling there instead of launching (the template arguments in
-// igg/fused_families.hpp stay the only place that names a variant's tiling).
-extern FusedTile* g_hx_tile_query;
 
-// Fused launches by tiling family and element type, one translation unit each
-// so they compile in parallel (the tiling-9 family with its side-only z forms
-// alone took 7.7 min as one unit of both types): fused_t0_<dt>.hip (variants
-// 0, 50), fused_t11_<dt>.hip (40, 42), fused_t9_<dt>.hip (9),
-// fused_t14_<dt>.hip (14, 44); the bodies are in igg/fused_families.hpp, each
-// unit instantiates one (family, type). Return false for a variant not in the
-// family.
-template <typename T>
-bool fused_family_t0(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
-template <typename T>
-bool fused_family_t11(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
-template <typename T>
-bool fused_family_t9(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
-template <typename T>
-bool fused_family_t14(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
+// Fused launches by tiling family and element type, one translation unit each so
+// they compile in parallel (igg/fused_families.hpp; the families' variants are the
+// rows of igg/variants.hpp). Return false for a variant not in the family.
+template <typename T> bool fused_family_t0(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
+template <typename T> bool fused_family_t11(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
+template <typename T> bool fused_family_t9(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
+template <typename T> bool fused_family_t14(const DiffusionArgs& d, const HaloIOArgs& io, int v, int mode, hipStream_t s);
 
 namespace {
 
@@ -204,15 +193,27 @@ __device__ __forceinline__ HxTile<T> hx_tile(const HxScal<T>& a, int64_t bid, in
 // sc0 sc1 also works but writes back the XCD's whole L2 from every storing
 // wave: +14 % per step, profiles/r3_coherence/.)
 
-// FEAT bits (compile-time exchange features): 1 x-in, 2 y-in, 4 z-in, 8 z-out,
-// 64 x-out, 128 y-out; 256 = non-temporal Cp loads (plain variants); 512 =
-// lane-distributed z-segment edge loads (plain variants, below); 1024 = one
-// workgroup per CU (launch); 2048 = no per-wave specialisation (kernel below);
-// 4096 = z edge values staged through LDS instead of v_readlane; HZ (262144) =
-// the whole-line z-edge store form (DiffusionArgs::halo_z). 207 = the full
-// exchange, 0 = the plain update (variants 21+); other subsets served the cost
-// bisect (profiles/r1_fused/feature_bisect_*).
-constexpr int HZ = 262144;
+// FEAT: the compile-time feature word of the sweep. Exchange bits, per dimension:
+// halo values read from the arena (_IN), send values stored to the receivers
+// (_OUT). EXCH_ALL (207) is the full exchange, 0 the plain update (variants
+// 21+), EXCH_DIRECT_Z (203) and EXCH_XY (195) launch_mode's forms without z-in /
+// without z; other subsets served the cost bisect (profiles/r1_fused/).
+constexpr int X_IN = 1, Y_IN = 2, Z_IN = 4, Z_OUT = 8, X_OUT = 64, Y_OUT = 128;
+constexpr int EXCH_ALL = X_IN | Y_IN | Z_IN | Z_OUT | X_OUT | Y_OUT;
+constexpr int EXCH_DIRECT_Z = EXCH_ALL & ~Z_IN, EXCH_XY = EXCH_ALL & ~(Z_IN | Z_OUT);
+// Extras of a tiling (the last column of its row in igg/variants.hpp):
+constexpr int NT_CP = 256;         // non-temporal Cp loads (plain variants)
+constexpr int ZSEG = 512;          // lane-distributed z-segment edge loads (plain variants; hx_sweep)
+constexpr int OCC1 = 1024;         // one workgroup per CU (launch_hx)
+constexpr int NO_SPEC = 2048;      // no per-wave specialisation (diffusion3d_hx_kernel)
+constexpr int Z_LDS = 4096;        // z edge values staged through LDS instead of v_readlane
+constexpr int Z_EDGE_LANE = 8192;  // the z edge without per-row cross-lane operations (ZE in hx_sweep)
+constexpr int HZ = 262144;         // the whole-line z-edge store form (DiffusionArgs::halo_z)
+// Measurement-only forms of rounds 1-2 (build.py --probes): two timing probes with
+// WRONG results that skip the z-segment edge loads / the y-halo row loads, the
+// reversed march (RV in hx_sweep, plain sweeps only), temporal stores of T2.
+constexpr int PROBE_NO_ZSEG = 16384, PROBE_NO_YROWS = 32768, PROBE_REVERSE = 65536, PROBE_T_STORE = 131072;
+constexpr int PROBE_BITS = PROBE_NO_ZSEG | PROBE_NO_YROWS | PROBE_REVERSE | PROBE_T_STORE;
 // Side-only z forms (chosen per wave by diffusion3d_hx_kernel when the tiling
 // has ZSIDES): a z-edge wave holds one z edge unless a row fits in one wave,
 // so the other side's per-row readlanes and selects are compiled out (ZLO:
@@ -231,7 +232,7 @@ constexpr int ZLO = 524288, ZHI = 1048576, ZSIDES = 2097152;
 // otherwise the readlane form runs).
 constexpr int ZDPP = 4194304;
 // OCC2 (round 6, launch only): at most 2 workgroups per CU, enforced with an
-// unused dynamic LDS allocation as FEAT 1024 does for one; the grid's chunks are
+// unused dynamic LDS allocation as OCC1 does for one; the grid's chunks are
 // sized for that residency. f32 tiling 0 gains 2.5 % (plain variant 44).
 constexpr int OCC2 = 8388608;
 
@@ -245,18 +246,16 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
          int64_t clip_hi = INT64_MAX) {
   using V = typename Vec<T, VZ>::type;
   constexpr int W = 64 * VZ * BZ;
-  // FEAT 16384 / 32768 / 65536 / 131072 are measurement-only forms (rounds
-  // 1-2, not adopted): compiled only with build.py --probes (IGG_PROBES).
 #ifndef IGG_PROBES
-  static_assert((FEAT & (16384 | 32768 | 65536 | 131072)) == 0, "measurement-only FEAT bits need IGG_PROBES");
+  static_assert((FEAT & PROBE_BITS) == 0, "measurement-only FEAT bits need IGG_PROBES");
 #endif
-  // FEAT 65536 (RV, plain sweeps only): reversed march - chunks from the top x
+  // PROBE_REVERSE (RV, plain sweeps only): reversed march - chunks from the top x
   // down and each chunk's planes from high x to low - for every other step of
   // the ping-pong loop, so a step starts on the planes the previous (forward)
   // step touched last, which may still sit in the memory-side Infinity Cache.
   // The x term is summed in the forward order: results are bitwise identical.
-  constexpr bool RV = (FEAT & 65536) != 0;
-  static_assert(!RV || (FEAT & (1 | 2 | 4 | 8 | 64 | 128 | 4096 | 8192)) == 0, "RV: plain sweeps only");
+  constexpr bool RV = (FEAT & PROBE_REVERSE) != 0;
+  static_assert(!RV || (FEAT & (EXCH_ALL | Z_LDS | Z_EDGE_LANE)) == 0, "RV: plain sweeps only");
   constexpr int64_t DX = RV ? -1 : 1;
   // Chunks holding the x send planes run first (order 0, last, 1, 2, ...): the
   // plane x=n0-2 is computed in the last step of the last chunk, so with >= 2
@@ -287,7 +286,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   if (zt >= hi2) return;
   // A wave that exchanges nothing runs the plain vector march (igg/vsweep.hpp):
   // 15 % less VALU than this loop's plain form, 2 % per step for tiling 11
-  // (profiles/r6_vsweep/). FEAT 512 (lane-distributed edge loads) only chose
+  // (profiles/r6_vsweep/). ZSEG (lane-distributed edge loads) only chose
   // how this loop's plain form fetched the segment edges: ignored there. Not
   // for 8-wave workgroups (tiling 43's full-row tiles): at <= 256 VGPRs the
   // vector march spills (4 VGPRs, 20 B scratch) and ran 4.5 % slower. Not for
@@ -295,8 +294,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   // 0.6 % slower (same-box A/B, profiles/r6_vsweep/). f64 only: the f32
   // restrict-form plain variants ran 2.5-6 % slower relative to the vector
   // kernel with it (1024^3).
-  constexpr int NOT_PLAIN =
-      1 | 2 | 4 | 8 | 64 | 128 | 256 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | ZSIDES;
+  constexpr int NOT_PLAIN = EXCH_ALL | NT_CP | Z_LDS | Z_EDGE_LANE | PROBE_BITS | ZSIDES;
   if constexpr ((FEAT & NOT_PLAIN) == 0 && BY * BZ <= 4 && sizeof(T) == 8) {
     v_sweep<T, RY, VZ, PF, true, (FEAT & HZ) != 0, true>(t2, t, cpp, n0, n1, n2, xs, xe, y0, nv, zt, 1, hi2, a.rdx2,
                                                          a.rdy2, a.rdz2, a.dtlam, a.zh_lo != 0, a.zh_hi != 0);
@@ -315,11 +313,11 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   const bool load_next = lane == 63 || z0 + VZ > zhi_v;
   const int zpi = static_cast<int>(max<int64_t>(zc - 1, 0) - zt);
   const int zni = static_cast<int>(min<int64_t>(zc + VZ, n2 - 1) - zt);
-  // FEAT 512: the z neighbours across the segment's ends (lane 0's prev, the
+  // ZSEG: the z neighbours across the segment's ends (lane 0's prev, the
   // load_next lanes' next: one uniform element per row each) are fetched by
   // lanes r / 32+r with ONE load per x step, one step ahead, and moved with
   // readlane - instead of 2*RY single-lane loads held in 2*RY registers.
-  static_assert(!(FEAT & 512) || RY <= 32, "FEAT 512: at most 32 rows per wave");
+  static_assert(!(FEAT & ZSEG) || RY <= 32, "ZSEG: at most 32 rows per wave");
   const int64_t zc63 = min<int64_t>(zt + 63 * VZ, zhi_v);
   const int zedge = lane < 32 ? static_cast<int>(max<int64_t>(zt - 1, 0) - zt)
                               : static_cast<int>(min<int64_t>(zc63 + VZ, n2 - 1) - zt);
@@ -332,12 +330,12 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   const T* ymb = t + (y0 - 1) * n2 + zt;
   const T* ypb = t + (y0 + nv) * n2 + zt;
   int64_t yms = s0, yps = s0;
-  if ((FEAT & 2) && y0 == 1 && yi0) { ymb = yi0 + zt; yms = n2; }
-  if ((FEAT & 2) && y0 + nv == n1 - 1 && yi1) { ypb = yi1 + zt; yps = n2; }
+  if ((FEAT & Y_IN) && y0 == 1 && yi0) { ymb = yi0 + zt; yms = n2; }
+  if ((FEAT & Y_IN) && y0 + nv == n1 - 1 && yi1) { ypb = yi1 + zt; yps = n2; }
   // y send rows of this wave.
-  T* const yrow0 = ((FEAT & 128) && y0 == 1 && yo0) ? yo0 + zt : nullptr;
+  T* const yrow0 = ((FEAT & Y_OUT) && y0 == 1 && yo0) ? yo0 + zt : nullptr;
   int ry1 = static_cast<int>(n1 - 2 - y0);
-  T* const yrow1 = ((FEAT & 128) && ry1 >= 0 && ry1 < nv && yo1) ? yo1 + zt : nullptr;
+  T* const yrow1 = ((FEAT & Y_OUT) && ry1 >= 0 && ry1 < nv && yo1) ? yo1 + zt : nullptr;
   if (!yrow1) ry1 = -1;
   // z edges of this wave: low edge in lane 0 (element 0 = halo z=0, element
   // 1 = send z=1), high edge in lane zh (element VZ-1 = halo, VZ-2 = send).
@@ -347,9 +345,9 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   const int zh = __builtin_amdgcn_readfirstlane(static_cast<int>((n2 - VZ - zt) / VZ));
   constexpr bool SLO = (FEAT & ZHI) == 0, SHI = (FEAT & ZLO) == 0;  // z sides this form handles
   constexpr bool ZD = (FEAT & ZDPP) != 0;
-  static_assert(!ZD || (RY <= 16 && (FEAT & (4096 | 8192)) == 0), "ZDPP: RY <= 16, not with the LDS / edge-lane forms");
-  const bool zin_lo = SLO && (FEAT & 4) && has_lo && zi0, zin_hi = SHI && (FEAT & 4) && has_hi && zi1;
-  const bool zout_lo = SLO && (FEAT & 8) && has_lo && zo0, zout_hi = SHI && (FEAT & 8) && has_hi && zo1;
+  static_assert(!ZD || (RY <= 16 && (FEAT & (Z_LDS | Z_EDGE_LANE)) == 0), "ZDPP: RY <= 16, not with the LDS / edge-lane forms");
+  const bool zin_lo = SLO && (FEAT & Z_IN) && has_lo && zi0, zin_hi = SHI && (FEAT & Z_IN) && has_hi && zi1;
+  const bool zout_lo = SLO && (FEAT & Z_OUT) && has_lo && zo0, zout_hi = SHI && (FEAT & Z_OUT) && has_hi && zo1;
   const bool zin = zin_lo || zin_hi, zout = zout_lo || zout_hi;
   // halo_z (FEAT HZ): this wave holds a z edge whose halo element it may write
   const bool hz_wave = (FEAT & HZ) != 0 && ((has_lo && a.zh_lo) || (has_hi && a.zh_hi));
@@ -374,16 +372,16 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   const bool remote = zout || yrow0 || yrow1 || (xs == 1 && xo0) || (xe == n0 - 1 && xo1);
   T znext = T(0), zv = T(0);
   if (zin) znext = zsrc[xs * a.zp];
-  // FEAT 4096: the z edge values move between the edge lane and the
+  // Z_LDS: the z edge values move between the edge lane and the
   // lane-distributed row layout through 4*RY LDS slots of this wave (in/out x
   // lo/hi) instead of v_readlane (whose SGPR result feeds VALU with wait states
   // that one wave per SIMD cannot hide: profiles/r2_fused_spec/).
   T* zs = nullptr;
-  if constexpr ((FEAT & 4096) != 0) {
+  if constexpr ((FEAT & Z_LDS) != 0) {
     __shared__ T zslots[BY * BZ * 4 * RY];
     zs = zslots + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (4 * RY);
   }
-  // FEAT 8192 (ZE): the z edge without per-row cross-lane operations. The
+  // Z_EDGE_LANE (ZE): the z edge without per-row cross-lane operations. The
   // halo values of the wave's rows are read by uniform-address loads (every
   // lane the same address: one request per row, or scalar loads), one x step
   // ahead, and selected into the edge lane; the edge lane's send values are
@@ -391,7 +389,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   // RY LDS slots of this wave to the lane-distributed layout of the (single,
   // coalesced) remote store. A wave with both z edges (n2 <= 64*VZ + VZ) is
   // not supported by this form (launch_mode falls back).
-  constexpr bool ZE = (FEAT & 8192) != 0;
+  constexpr bool ZE = (FEAT & Z_EDGE_LANE) != 0;
   const T* zi_base = zin_lo ? zi0 : zi1;
   T zi_cur[ZE ? RY : 1], zi_nxt[ZE ? RY : 1];
   T* zo_lds = nullptr;
@@ -412,16 +410,16 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
   T* zsend_dst = nullptr;
 
   auto plane = [&](int64_t X) -> const T* {
-    if constexpr ((FEAT & 1) != 0) {
+    if constexpr ((FEAT & X_IN) != 0) {
       if (X == 0 && xi0) return xi0;
       if (X == n0 - 1 && xi1) return xi1;
     }
     return t + X * s0;
   };
-  // Cp is streamed once (no reuse): FEAT bit 256 loads it non-temporally so it
+  // Cp is streamed once (no reuse): NT_CP loads it non-temporally so it
   // does not displace the T lines that neighbouring waves re-read (y/z halos).
   auto ldc = [&](const T* p) -> V {
-    if constexpr ((FEAT & 256) != 0) return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
+    if constexpr ((FEAT & NT_CP) != 0) return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
     return vld<T, VZ>(p);
   };
   // tm / tp: the planes behind / ahead of the march (x - DX / x + DX)
@@ -435,20 +433,18 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
     cp[r] = ldc(cpp + xf * s0 + rowb[r] + zl);
   }
   T evn = T(0);
-  if constexpr ((FEAT & 512) != 0 && (FEAT & 16384) == 0) evn = t[xf * s0 + rowe];
+  if constexpr ((FEAT & ZSEG) != 0 && (FEAT & PROBE_NO_ZSEG) == 0) evn = t[xf * s0 + rowe];
   int64_t x = xf;
   for (int64_t i = 0; i < len; ++i, x += DX) {
     const int64_t off = x * s0;
     T evc = T(0);
-    if constexpr ((FEAT & 512) != 0) {
+    if constexpr ((FEAT & ZSEG) != 0) {
       evc = evn;
-      if constexpr ((FEAT & 16384) == 0) {
+      if constexpr ((FEAT & PROBE_NO_ZSEG) == 0) {
         if (i + 1 < len) evn = t[off + DX * s0 + rowe];
       }
 #ifdef IGG_PROBES
-      // FEAT 16384 / 32768: timing probes (results WRONG): skip the z-segment
-      // edge loads / the y-halo row loads, to price the tile-edge re-fetch.
-      if constexpr ((FEAT & 16384) != 0) evn = evn * T(0.5);
+      if constexpr ((FEAT & PROBE_NO_ZSEG) != 0) evn = evn * T(0.5);  // timing probe (results WRONG)
 #endif
     }
     // z halo of plane x (fetched one step ahead), prefetch plane x+1's. (The
@@ -466,7 +462,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
     } else if (zin) {
       zcur = znext;
       if (x + 1 < xe) znext = zsrc[(x + 1) * a.zp];
-      if constexpr ((FEAT & 4096) != 0) {
+      if constexpr ((FEAT & Z_LDS) != 0) {
         // through the wave's LDS slots: no v_readlane -> SGPR -> VALU chain
         if (lo_l || hi_l) zs[(lane < 32 ? 0 : RY) + rl] = zcur;
 #pragma unroll
@@ -485,13 +481,13 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
         ph = zin_hi && lane == zh;
       }
     }
-    T* const xd0 = (FEAT & 64) && x == 1 ? xo0 : nullptr;
-    T* const xd1 = (FEAT & 64) && x == n0 - 2 ? xo1 : nullptr;
+    T* const xd0 = (FEAT & X_OUT) && x == 1 ? xo0 : nullptr;
+    T* const xd1 = (FEAT & X_OUT) && x == n0 - 2 ? xo1 : nullptr;
     V tn[RY], cpn[RY];
     if (PF) {
       const int64_t xn = RV ? max<int64_t>(x - 2, 0) : min(x + 2, n0 - 1);
       const int64_t xc = RV ? max<int64_t>(x - 1, xs) : min(x + 1, xe - 1);
-      const T* pn = ((FEAT & 1) && xn == n0 - 1 && xi1) ? xi1 : t + xn * s0;
+      const T* pn = ((FEAT & X_IN) && xn == n0 - 1 && xi1) ? xi1 : t + xn * s0;
 #pragma unroll
       for (int r = 0; r < RY; ++r) {
         tn[r] = vld<T, VZ>(pn + rowb[r] + zl);
@@ -499,18 +495,18 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
       }
     }
     V ym, yp;
-    if constexpr ((FEAT & 32768) == 0) {
+    if constexpr ((FEAT & PROBE_NO_YROWS) == 0) {
       ym = vld<T, VZ>(ymb + x * yms + zl);
       yp = vld<T, VZ>(ypb + x * yps + zl);
     }
 #ifdef IGG_PROBES
-    if constexpr ((FEAT & 32768) != 0) {  // timing probe (results WRONG)
+    if constexpr ((FEAT & PROBE_NO_YROWS) != 0) {  // timing probe (results WRONG)
       ym = tc[0];
       yp = tc[RY - 1];
     }
 #endif
     T em[RY], ep[RY];
-    if constexpr ((FEAT & 512) == 0) {
+    if constexpr ((FEAT & ZSEG) == 0) {
 #pragma unroll
       for (int r = 0; r < RY; ++r) {
         em[r] = load_prev ? t[off + rowb[r] + zpi] : T(0);
@@ -526,10 +522,10 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
     T zo_buf[ZE ? RY : 1];
 #pragma unroll
     for (int r = 0; r < RY; ++r) {
-      if constexpr (ZE && (FEAT & 4) != 0) {
+      if constexpr (ZE && (FEAT & Z_IN) != 0) {
         tc[r][0] = ze_lo ? zi_cur[r] : tc[r][0];
         tc[r][VZ - 1] = ze_hi ? zi_cur[r] : tc[r][VZ - 1];
-      } else if constexpr (ZD && (FEAT & 4) != 0) {
+      } else if constexpr (ZD && (FEAT & Z_IN) != 0) {
         if constexpr (SLO) {
           const T vl = row_shl(zcur, r);  // lane 0 <- lane r
           tc[r][0] = pl ? vl : tc[r][0];
@@ -538,7 +534,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
           const T vh = row_shr(zcur, r);  // lane zh <- lane zh - r
           tc[r][VZ - 1] = ph ? vh : tc[r][VZ - 1];
         }
-      } else if constexpr ((FEAT & 4) != 0 && (FEAT & 4096) == 0) {
+      } else if constexpr ((FEAT & Z_IN) != 0 && (FEAT & Z_LDS) == 0) {
         // z halo patch of row r right before its update, branch-free: patching
         // every row up front made the step wait for all of this plane's loads
         // at once (and per-row branches split the body into blocks the
@@ -557,7 +553,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
       const V& yn = (r + 1 < nv) ? tc[(r + 1 < RY) ? r + 1 : r] : yp;
       T prev = __shfl_up(c[VZ - 1], 1);
       T next = __shfl_down(c[0], 1);
-      if constexpr ((FEAT & 512) != 0) {
+      if constexpr ((FEAT & ZSEG) != 0) {
         const T pv = lane_read(evc, r), nx = lane_read(evc, 32 + r);
         if (load_prev) prev = pv;
         if (load_next) next = nx;
@@ -588,9 +584,9 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
         }
         if (lane_full || ((FEAT & HZ) != 0 && zfull)) {
 #ifdef IGG_PROBES
-          // FEAT 131072: plain (temporal) stores, to measure what the
+          // PROBE_T_STORE: plain (temporal) stores, to measure what the
           // non-temporal hint costs or saves in the Infinity Cache
-          if constexpr ((FEAT & 131072) != 0) *reinterpret_cast<V*>(dst) = out;
+          if constexpr ((FEAT & PROBE_T_STORE) != 0) *reinterpret_cast<V*>(dst) = out;
           else
 #endif
           __builtin_nontemporal_store(out, reinterpret_cast<V*>(dst));
@@ -612,12 +608,12 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
           if (DF && !yrow0) { ysend = out; ysend_dst = zown ? yrow1 + x * n2 + zl : nullptr; }
           else if (zown) st_sys_at(yrow1, static_cast<uint32_t>((x * n2 + zl) * sizeof(T)), out);
         }
-        if constexpr (ZE && (FEAT & 8) != 0) {
+        if constexpr (ZE && (FEAT & Z_OUT) != 0) {
           zo_buf[r] = has_lo ? out[1] : out[VZ - 2];  // the send element of the edge lane
-        } else if constexpr ((FEAT & 4096) != 0) {
+        } else if constexpr ((FEAT & Z_LDS) != 0) {
           if (zout_lo && lane == 0) zs[2 * RY + r] = out[1];
           if (zout_hi && lane == zh) zs[3 * RY + r] = out[VZ - 2];
-        } else if constexpr (ZD && (FEAT & 8) != 0) {
+        } else if constexpr (ZD && (FEAT & Z_OUT) != 0) {
           if constexpr (SLO) {
             const T vl = row_shr(out[1], r);  // lane r <- lane 0
             zv = (zout_lo && lane == r) ? vl : zv;
@@ -626,7 +622,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
             const T vh = row_shl(out[VZ - 2], r);  // lane zh - r <- lane zh
             zv = (zout_hi && lane == zh - r) ? vh : zv;
           }
-        } else if constexpr ((FEAT & 8) != 0) {
+        } else if constexpr ((FEAT & Z_OUT) != 0) {
           // branch-free (see the z-in patch): unconditional readlanes + selects
           if constexpr (SLO) {
             const T vl = lane_read(out[1], 0);
@@ -639,10 +635,10 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
         }
       }
     }
-    if constexpr ((FEAT & 4096) != 0) {
+    if constexpr ((FEAT & Z_LDS) != 0) {
       if (zdst) zv = zs[(lane < 32 ? 2 * RY : 3 * RY) + rl];
     }
-    if constexpr (ZE && (FEAT & 8) != 0) {
+    if constexpr (ZE && (FEAT & Z_OUT) != 0) {
       if (zout) {  // uniform: one transpose through LDS per step
         if (lane == (zout_lo ? 0 : zh)) {
 #pragma unroll
@@ -665,7 +661,7 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
       }
     }
     if (!PF && i + 1 < len) {
-      const T* pn = ((FEAT & 1) && x + 2 == n0 - 1 && xi1) ? xi1 : t + (x + 2 * DX) * s0;
+      const T* pn = ((FEAT & X_IN) && x + 2 == n0 - 1 && xi1) ? xi1 : t + (x + 2 * DX) * s0;
 #pragma unroll
       for (int r = 0; r < RY; ++r) {
         tp[r] = vld<T, VZ>(pn + rowb[r] + zl);
@@ -697,15 +693,15 @@ hx_sweep(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
 #else
 #define IGG_HX_OCC_ATTR
 #endif
-template <typename T, int BY, int RY, int VZ, bool PF, int BZ, bool DF, int FEAT = 207>
+template <typename T, int BY, int RY, int VZ, bool PF, int BZ, bool DF, int FEAT = EXCH_ALL>
 __global__ void __launch_bounds__(64 * BY * BZ) IGG_HX_OCC_ATTR
 diffusion3d_hx_kernel(T* __restrict__ t2, const T* __restrict__ t, const T* __restrict__ cpp,
                       const T* __restrict__ xi0, const T* __restrict__ xi1, const T* __restrict__ yi0,
                       const T* __restrict__ yi1, const T* __restrict__ zi0, const T* __restrict__ zi1,
                       T* __restrict__ xo0, T* __restrict__ xo1, T* __restrict__ yo0, T* __restrict__ yo1,
                       T* __restrict__ zo0, T* __restrict__ zo1, const HxScal<T> a) {
-  constexpr int FX = FEAT & (1 | 64), FY = FEAT & (2 | 128), FZ = FEAT & (4 | 8);
-  constexpr int FK = FEAT & ~(1 | 2 | 4 | 8 | 64 | 128);
+  constexpr int FX = FEAT & (X_IN | X_OUT), FY = FEAT & (Y_IN | Y_OUT), FZ = FEAT & (Z_IN | Z_OUT);
+  constexpr int FK = FEAT & ~EXCH_ALL;
 #define IGG_HX_SWEEP(F)                                                                                  \
   hx_sweep<T, BY, RY, VZ, PF, BZ, DF, (F)>(t2, t, cpp, xi0, xi1, yi0, yi1, zi0, zi1, xo0, xo1, yo0, yo1, \
                                            zo0, zo1, a)
@@ -722,8 +718,8 @@ diffusion3d_hx_kernel(T* __restrict__ t2, const T* __restrict__ t, const T* __re
 #define IGG_HX_SWEEP_R(F)                                                                                \
   hx_sweep<T, BY, RY, VZ, PF, BZ, DF, (F)>(t2, t, cpp, xi0, xi1, yi0, yi1, zi0, zi1, xo0, xo1, yo0, yo1, \
                                            zo0, zo1, a, clo, chi)
-  if constexpr ((FX | FY | FZ) == 0 || (FEAT & 2048) != 0) {
-    IGG_HX_SWEEP(FEAT);  // nothing to specialise, or specialisation disabled (FEAT 2048)
+  if constexpr ((FX | FY | FZ) == 0 || (FEAT & NO_SPEC) != 0) {
+    IGG_HX_SWEEP(FEAT);  // nothing to specialise, or specialisation disabled (NO_SPEC)
   } else {
     constexpr int W = 64 * VZ * BZ;
     const HxTile<T> tile = hx_tile(a, blockIdx.x, gridDim.x);
@@ -849,7 +845,7 @@ int resident(const void* kernel, int block, size_t lds = 0) {
 template <int BY, int RY, int VZ, int BZ, int FEAT>
 int64_t hx_feature_wgs(int64_t n0, int64_t n1, int64_t n2, int64_t ch, int64_t nty, int64_t ntz,
                        const HaloIOArgs& io) {
-  constexpr int FX = FEAT & (1 | 64), FY = FEAT & (2 | 128), FZ = FEAT & (4 | 8);
+  constexpr int FX = FEAT & (X_IN | X_OUT), FY = FEAT & (Y_IN | Y_OUT), FZ = FEAT & (Z_IN | Z_OUT);
   constexpr int W = 64 * VZ * BZ;
   auto on = [&](int d, int s) { return io.in[d][s] != 0 || io.out[d][s] != 0; };
   const int64_t nch = (n0 - 2 + ch - 1) / ch;
@@ -883,7 +879,7 @@ inline bool zh_side(const HaloIOArgs& io, int s) {
   return io.zh[s] >= 0 ? io.zh[s] != 0 : (io.in[2][s] != 0 || io.out[2][s] == 0);
 }
 
-template <typename T, int BY, int RY, int VZ, bool PF, int BZ, bool DF, int FEAT = 207>
+template <typename T, int BY, int RY, int VZ, bool PF, int BZ, bool DF, int FEAT = EXCH_ALL>
 void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream, bool peel = false,
                bool order = false) {
   const int64_t n0 = d.n[0], n1 = d.n[1], n2 = d.n[2];
@@ -898,12 +894,12 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
   a.nty = (n1 - 2 + TY - 1) / TY;
   const int64_t len0 = n0 - 2, tiles = a.ntz * a.nty;
   const int rounds = d.rounds > 0 ? d.rounds : 1;
-  // FEAT 1024: one workgroup per CU, enforced with an unused dynamic LDS
-  // allocation (isolates the occupancy effect of the lower-VGPR FEAT 512 form).
-  size_t lds = (FEAT & 1024) ? 96 * 1024 : ((FEAT & OCC2) ? 79 * 1024 : 0);
+  // OCC1: one workgroup per CU, enforced with an unused dynamic LDS
+  // allocation (isolates the occupancy effect of the lower-VGPR ZSEG form).
+  size_t lds = (FEAT & OCC1) ? 96 * 1024 : ((FEAT & OCC2) ? 79 * 1024 : 0);
   // Measurement knob: IGG_HX_WG_PER_CU=k caps the resident workgroups per CU at
   // k (dynamic LDS of 160 KiB / k), which also sizes the chunks of the grid.
-  if (const char* e = std::getenv("IGG_HX_WG_PER_CU"); e && (FEAT & 1024) == 0) {
+  if (const char* e = std::getenv("IGG_HX_WG_PER_CU"); e && (FEAT & OCC1) == 0) {
     const int k = std::atoi(e);
     if (k > 0) lds = std::max<size_t>(lds, (160 * 1024) / static_cast<size_t>(k) - 1024);
   }
@@ -920,7 +916,7 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
   a.stamps = g_hx_stamps;
   a.force_sel = g_hx_force_sel;
   a.peel = peel ? 1 : 0;
-  constexpr int FZ_ = FEAT & (4 | 8);
+  constexpr int FZ_ = FEAT & (Z_IN | Z_OUT);
   a.order = order ? 1 : 0;
   a.order_lo = (FZ_ != 0 && (io.in[2][0] || io.out[2][0])) ? 1 : 0;
   a.order_hi = (FZ_ != 0 && (io.in[2][1] || io.out[2][1])) ? 1 : 0;
@@ -935,8 +931,8 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
   a.sync = StepSync{};
   // In-kernel step sync: the specialised kernel only (per-wave feature
   // classes), and not under the diagnostics that override the classes.
-  constexpr int FXYZ = FEAT & (1 | 2 | 4 | 8 | 64 | 128);
-  if (io.sync.my_flags && FXYZ != 0 && (FEAT & 2048) == 0 && !a.stamps && a.force_sel < 0) {
+  constexpr int FXYZ = FEAT & EXCH_ALL;
+  if (io.sync.my_flags && FXYZ != 0 && (FEAT & NO_SPEC) == 0 && !a.stamps && a.force_sel < 0) {
     a.sync = io.sync;
     // counted per workgroup (step_sync_exit_wg)
     a.sync.feat_waves = hx_feature_wgs<BY, RY, VZ, BZ, FEAT>(n0, n1, n2, a.ch, a.nty, a.ntz, io);
@@ -960,10 +956,10 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
 //
 // Mode bit 2 (modes 2/3 = 0/1 + 2): without a z neighbour (dims[2] == 1 and
 // not periodic: the 2x1x1 and 2x2x1 topologies of 2 and 4 ranks) the z-edge
-// exchange is compiled out (FEAT 195 = x/y in/out). Results are identical (207
+// exchange is compiled out (EXCH_XY = x/y in/out). Results are identical (EXCH_ALL
 // skips the null z sides at run time). It pays for the 255-VGPR tiling 11
-// (loopback 2x2x1 interior rank: 0.632 vs 0.651 ms for the best 207 form) but
-// the other tilings' 195 forms measured slower than their 207 forms
+// (loopback 2x2x1 interior rank: 0.632 vs 0.651 ms for the best EXCH_ALL form) but
+// the other tilings' EXCH_XY forms measured slower than their EXCH_ALL forms
 // (profiles/r1_noz/), so it is an A/B choice, not automatic.
 //
 // Mode bit 4 (direct z, FusedHalo with registered field buffers): the z-face
@@ -979,13 +975,9 @@ void launch_hx(const DiffusionArgs& d, const HaloIOArgs& io, hipStream_t stream,
 // Mode bit 8 (peel): a wave of an x-exchange chunk sweeps x = 1 and x = n0-2
 // with the x features and the planes in between without them (the x code in
 // the loop slows the whole chunk's march: profiles/r2_f32_fused/ class 1).
-// XF: extra FEAT bits of the tiling (512 | 1024 for fused variant 40).
+// XF: extra FEAT bits of the tiling (ZSEG | OCC1 for fused variant 40).
 template <typename T, int BY, int RY, int VZ, bool PF, int BZ, int XF = 0>
 void launch_mode(const DiffusionArgs& d, const HaloIOArgs& io, int mode, hipStream_t s) {
-  if (g_hx_tile_query) {  // diffusion3d_fused_tile: report the tiling, launch nothing
-    *g_hx_tile_query = FusedTile{BY, RY, VZ, BZ, (XF & ZDPP) != 0};
-    return;
-  }
   if constexpr ((XF & ZDPP) != 0) {
     // the DPP z form: one z edge per wave, and the high edge's rows (lanes
     // zh - r) inside the edge lane's 16-lane DPP row
@@ -994,10 +986,10 @@ void launch_mode(const DiffusionArgs& d, const HaloIOArgs& io, int mode, hipStre
       return;
     }
   }
-  if constexpr ((XF & 8192) != 0) {
+  if constexpr ((XF & Z_EDGE_LANE) != 0) {
     // the edge-lane z form needs every wave to hold at most one z edge
     if (zedge_one_wave(d.n[2], VZ)) {
-      launch_mode<T, BY, RY, VZ, PF, BZ, (XF & ~8192)>(d, io, mode, s);
+      launch_mode<T, BY, RY, VZ, PF, BZ, (XF & ~Z_EDGE_LANE)>(d, io, mode, s);
       return;
     }
   }
@@ -1006,7 +998,7 @@ void launch_mode(const DiffusionArgs& d, const HaloIOArgs& io, int mode, hipStre
   const bool ord = (mode & 32) != 0;  // z-edge tiles first (hx_tile)
   mode &= 7;
   if ((mode & 4) && zx) {
-    // Direct z (FEAT 203 = 207 without z-in): the z sends land in the
+    // Direct z (EXCH_DIRECT_Z = EXCH_ALL without z-in): the z sends land in the
     // receivers' field halo elements, so the z-edge waves read their halo
     // from the field like every other wave and carry only the send code.
     if (io.in[2][0] || io.in[2][1]) fail("diffusion3d (fused halo): direct z mode with z arena input");
@@ -1015,16 +1007,16 @@ void launch_mode(const DiffusionArgs& d, const HaloIOArgs& io, int mode, hipStre
     for (int sd = 0; sd < 2; ++sd)
       if (d.halo_z && io.out[2][sd] && !io.z_out_arena && zh_side(io, sd))
         fail("diffusion3d (fused halo): whole-line z-edge stores on a direct-z side (HaloIOArgs::zh)");
-    if (mode & 1) launch_hx<T, BY, RY, VZ, PF, BZ, true, 203 | XF | HZ>(d, io, s, pk, ord);
-    else launch_hx<T, BY, RY, VZ, PF, BZ, false, 203 | XF | HZ>(d, io, s, pk, ord);
+    if (mode & 1) launch_hx<T, BY, RY, VZ, PF, BZ, true, EXCH_DIRECT_Z | XF | HZ>(d, io, s, pk, ord);
+    else launch_hx<T, BY, RY, VZ, PF, BZ, false, EXCH_DIRECT_Z | XF | HZ>(d, io, s, pk, ord);
   } else if (zx || !(mode & 2)) {
     mode &= 1;
-    if (mode == 0) launch_hx<T, BY, RY, VZ, PF, BZ, false, 207 | XF | HZ>(d, io, s, pk, ord);
-    else launch_hx<T, BY, RY, VZ, PF, BZ, true, 207 | XF | HZ>(d, io, s, pk, ord);
+    if (mode == 0) launch_hx<T, BY, RY, VZ, PF, BZ, false, EXCH_ALL | XF | HZ>(d, io, s, pk, ord);
+    else launch_hx<T, BY, RY, VZ, PF, BZ, true, EXCH_ALL | XF | HZ>(d, io, s, pk, ord);
   } else {
     mode &= 1;
-    if (mode == 0) launch_hx<T, BY, RY, VZ, PF, BZ, false, 195 | XF | HZ>(d, io, s, pk, ord);
-    else launch_hx<T, BY, RY, VZ, PF, BZ, true, 195 | XF | HZ>(d, io, s, pk, ord);
+    if (mode == 0) launch_hx<T, BY, RY, VZ, PF, BZ, false, EXCH_XY | XF | HZ>(d, io, s, pk, ord);
+    else launch_hx<T, BY, RY, VZ, PF, BZ, true, EXCH_XY | XF | HZ>(d, io, s, pk, ord);
   }
 }
 

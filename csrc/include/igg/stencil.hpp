@@ -53,7 +53,7 @@ struct DiffusionArgs {
 // under the build's flags: what the two-step pass computes per point itself.
 void launch_quotient(uintptr_t q, uintptr_t cp, int64_t n, double dt_lam, int elem_bytes, hipStream_t stream);
 
-// Number of tuned kernel variants (see stencil_kernels.hip); variant 0 = default.
+// Number of tuned kernel variants (the catalogue: igg/variants.hpp); variant 0 = default.
 int diffusion3d_num_variants();
 // Whether variant v is compiled in this build (measurement-only forms need build.py --probes).
 bool stencil_variant_compiled(int v);
@@ -139,7 +139,8 @@ struct HaloIOArgs {
   bool* sync_used = nullptr;
 };
 bool diffusion3d_fused_variant_ok(int v);
-// Tiling of fused variant v: a workgroup of by x bz waves, each wave ry rows of
+std::vector<int> diffusion3d_fused_variants();  // igg/variants.hpp: all of them, ascending, compiled or not
+// Tiling of fused variant v (its catalogue row): a workgroup of by x bz waves, each wave ry rows of
 // 64 vectors of vz points; dpp: the z edge moves as DPP row shifts where the
 // shape admits it (igg/zedge.hpp zedge_dpp_ok). Host arithmetic, no launch.
 struct FusedTile {
@@ -153,7 +154,7 @@ FusedTile diffusion3d_fused_tile(int v);
 // (-1: per-wave choice). Applies to subsequent fused launches.
 void fused_debug(int64_t* stamps, int force_sel);
 // Inner-box update through the fused kernel without exchange features
-// (tiling = a fused-capable variant index); used by the "hx" variants.
+// (tiling = a restrict-form tiling id of igg/variants.hpp); used by the "hx" variants.
 void launch_diffusion3d_inner_hx(const DiffusionArgs& a, int tiling, hipStream_t stream);
 // mode 0: sends stored as computed; 1: deferred one x step; + 2: z-edge exchange
 // compiled out when there is no z neighbour; + 4: no z receive code (direct z,

@@ -1,4 +1,4 @@
-// Fused halo-exchange diffusion kernels, tiling 0: fused variants 0, 50 (double).
+// Fused halo-exchange diffusion kernels, tiling 0: the rows of IGG_FUSED_T0 (igg/variants.hpp), double.
 // One (family, element type) per translation unit: igg/fused_families.hpp.
 #include "igg/fused_families.hpp"
 

@@ -1,4 +1,4 @@
-// Fused halo-exchange diffusion kernels, tiling 11: fused variants 40, 42 (double).
+// Fused halo-exchange diffusion kernels, tiling 11: the rows of IGG_FUSED_T11 (igg/variants.hpp), double.
 // One (family, element type) per translation unit: igg/fused_families.hpp.
 #include "igg/fused_families.hpp"
 

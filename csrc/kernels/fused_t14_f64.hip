@@ -1,4 +1,4 @@
-// Fused halo-exchange diffusion kernels, tiling 14: fused variants 14, 44 (double).
+// Fused halo-exchange diffusion kernels, tiling 14: the rows of IGG_FUSED_T14 (igg/variants.hpp), double.
 // One (family, element type) per translation unit: igg/fused_families.hpp.
 #include "igg/fused_families.hpp"
 

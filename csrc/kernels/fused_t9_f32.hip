@@ -1,4 +1,4 @@
-// Fused halo-exchange diffusion kernels, tiling 9 with side-only z forms: fused variant 9 (float).
+// Fused halo-exchange diffusion kernels, tiling 9 with side-only z forms: the rows of IGG_FUSED_T9 (igg/variants.hpp), float.
 // One (family, element type) per translation unit: igg/fused_families.hpp.
 #include "igg/fused_families.hpp"
 

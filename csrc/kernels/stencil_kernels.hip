@@ -21,6 +21,7 @@
 
 #include "igg/devmath.hpp"
 #include "igg/stencil.hpp"
+#include "igg/variants.hpp"
 #include "igg/xcd.hpp"
 
 namespace igg {
@@ -284,76 +285,6 @@ diffusion3d_vkernel(const KArgs<T> a, const BoxTable bt) {
   }
 }
 
-struct Variant {
-  const char* name;
-  int by, ry, vz;  // vz = 1: scalar kernel
-  bool pf, nt;
-};
-
-// Tuned variants; keep in sync with dispatch() below. Default (0) is the best
-// measured on MI355X for 512^3 f64 (benchmarks/stencil_sweep.py).
-constexpr Variant VARIANTS[] = {
-    {"v4_by4_ry4_nt", 4, 4, 4, false, true},     // 0
-    {"s_by4_ry8", 4, 8, 1, false, false},        // 1 (scalar fallback family)
-    {"v2_by4_ry4_pf_nt", 4, 4, 2, true, true},   // 2
-    {"v4_by4_ry4", 4, 4, 4, false, false},       // 3
-    {"v4_by4_ry4_pf_nt", 4, 4, 4, true, true},   // 4
-    {"v4_by4_ry2_nt", 4, 2, 4, false, true},     // 5
-    {"v8_by4_ry2_nt", 4, 2, 8, false, true},     // 6
-    {"v4_by2_ry4_nt", 2, 4, 4, false, true},     // 7
-    {"v4_by8_ry2_nt", 8, 2, 4, false, true},     // 8
-    {"v4_by4_ry8_nt", 4, 8, 4, false, true},     // 9
-    {"v8_by2_ry2_nt", 2, 2, 8, false, true},     // 10
-    {"v2_by4_ry8_nt", 4, 8, 2, false, true},     // 11
-    {"v4_bz2_by8_ry4_nt", 8, 4, 4, false, true}, // 12 (1024-thread blocks)
-    {"v4_bz2_by4_ry4_nt", 4, 4, 4, false, true}, // 13
-    {"v4_bz2_by2_ry8_nt", 2, 8, 4, false, true}, // 14
-    {"v2_bz2_by4_ry8_nt", 4, 8, 2, false, true}, // 15
-    {"v4_bz2_by8_ry2_nt", 8, 2, 4, false, true}, // 16
-    {"v2_bz4_by4_ry4_nt", 4, 4, 2, false, true}, // 17
-    {"s_by4_ry1", 4, 1, 1, false, false},        // 18 (low-VGPR: thin send planes)
-    {"v2_by4_ry1_nt", 4, 1, 2, false, true},     // 19 (low-VGPR vector)
-    {"v4_by4_ry2", 4, 2, 4, false, false},       // 20
-    // 21-25: inner box through the restrict-argument kernel of fused_kernels.hip
-    // with the tiling of variant 0/2/9/11/14 (other boxes: that variant here).
-    {"hx_v4_by4_ry4_nt", 4, 4, 4, false, true},     // 21
-    {"hx_v2_by4_ry4_pf_nt", 4, 4, 2, true, true},   // 22
-    {"hx_v4_by4_ry8_nt", 4, 8, 4, false, true},     // 23
-    {"hx_v2_by4_ry8_nt", 4, 8, 2, false, true},     // 24
-    {"hx_v4_bz2_by2_ry8_nt", 2, 8, 4, false, true}, // 25
-    // 26-31: tilings only in the restrict form (fallback for other boxes: the
-    // nearest stencil_kernels.hip variant)
-    {"hx_v2_by2_ry8_nt", 2, 8, 2, false, true},     // 26
-    {"hx_v2_by4_ry6_nt", 4, 6, 2, false, true},     // 27
-    {"hx_v2_by4_ry8_pf_nt", 4, 8, 2, true, true},   // 28
-    {"hx_v2_by4_ry4_nt", 4, 4, 2, false, true},     // 29
-    {"hx_v4_by4_ry2_nt", 4, 2, 4, false, true},     // 30
-    {"hx_v2_by8_ry4_nt", 8, 4, 2, false, true},     // 31
-    // 32-35: restrict form with non-temporal Cp loads (tilings of 11, 0, 9, 14)
-    {"hx_v2_by4_ry8_nt_ntc", 4, 8, 2, false, true},     // 32
-    {"hx_v4_by4_ry4_nt_ntc", 4, 4, 4, false, true},     // 33
-    {"hx_v4_by4_ry8_nt_ntc", 4, 8, 4, false, true},     // 34
-    {"hx_v4_bz2_by2_ry8_nt_ntc", 2, 8, 4, false, true}, // 35
-    // 36-39: restrict form with lane-distributed z-segment edge loads (tilings of 11, 9, 26, 0)
-    {"hx_v2_by4_ry8_nt_zl", 4, 8, 2, false, true},      // 36
-    {"hx_v4_by4_ry8_nt_zl", 4, 8, 4, false, true},      // 37
-    {"hx_v2_by2_ry8_nt_zl", 2, 8, 2, false, true},      // 38
-    {"hx_v4_by4_ry4_nt_zl", 4, 4, 4, false, true},      // 39
-    {"hx_v2_by4_ry8_nt_zl_occ1", 4, 8, 2, false, true}, // 40 (one workgroup per CU)
-    {"hx_v2_by4_ry10_nt_zl_occ1", 4, 10, 2, false, true}, // 41
-    {"hx_v2_by4_ry12_nt_zl_occ1", 4, 12, 2, false, true}, // 42
-    // 43: full-row z tiles (BZ 4 x 64 lanes x VZ 2 = 512 points, profiles/r2_fullrow/)
-    {"hx_v2_bz4_by2_ry8_nt", 2, 8, 2, false, true},     // 43
-    // 44: tiling 0 at most 2 workgroups per CU (f32 1024^3: 2.5 % ahead of its
-    // 3-per-CU form, profiles/r6_vsweep/)
-    {"hx_v4_by4_ry4_nt_occ2", 4, 4, 4, false, true},    // 44
-};
-// Variants 21..31: restrict-form tiling id (fused_kernels.hip dispatch_plain)
-// and the stencil_kernels.hip variant used for boxes other than the inner box.
-constexpr int HX_TILING[] = {0, 2, 9, 11, 14, 100, 101, 102, 103, 104, 105, 110, 111, 112, 113, 120, 121, 122, 123, 124, 125, 126, 141, 150};
-constexpr int HX_FALLBACK[] = {0, 2, 9, 11, 14, 11, 11, 11, 2, 5, 11, 11, 0, 9, 14, 11, 9, 11, 0, 11, 11, 11, 11, 0};
-constexpr int NVARIANTS = sizeof(VARIANTS) / sizeof(VARIANTS[0]);
-
 // Grid sizing policy: `g_rounds` full residency rounds (resident workgroups =
 // occupancy x CUs); the x-march is chunked so every block gets equal work and
 // no partial last round leaves CUs idle. g_rounds <= 0: fixed 4096-block target.
@@ -459,32 +390,27 @@ void launch_vector(const KArgs<T>& ka, const std::vector<Box>& boxes, hipStream_
   }
 }
 
+// The kernels of the catalogue (igg/variants.hpp), CORE rows first: the order of
+// first use is the order of the kernels in the code object, in a --probes build too.
 template <typename T>
 void dispatch(const KArgs<T>& ka, const std::vector<Box>& boxes, int v, hipStream_t s) {
   switch (v) {
-    case 0: launch_vector<T, 4, 4, 4, false, true>(ka, boxes, s); break;
-    case 1: launch_scalar<T, 4, 8, true>(ka, boxes, s); break;
-    case 2: launch_vector<T, 4, 4, 2, true, true>(ka, boxes, s); break;
-    case 5: launch_vector<T, 4, 2, 4, false, true>(ka, boxes, s); break;
-    case 9: launch_vector<T, 4, 8, 4, false, true>(ka, boxes, s); break;
-    case 11: launch_vector<T, 4, 8, 2, false, true>(ka, boxes, s); break;
-    case 14: launch_vector<T, 2, 8, 4, false, true, 2>(ka, boxes, s); break;
-    case 18: launch_scalar<T, 4, 1, true>(ka, boxes, s); break;
-#ifdef IGG_PROBES
-    case 3: launch_vector<T, 4, 4, 4, false, false>(ka, boxes, s); break;
-    case 4: launch_vector<T, 4, 4, 4, true, true>(ka, boxes, s); break;
-    case 6: launch_vector<T, 4, 2, 8, false, true>(ka, boxes, s); break;
-    case 7: launch_vector<T, 2, 4, 4, false, true>(ka, boxes, s); break;
-    case 8: launch_vector<T, 8, 2, 4, false, true>(ka, boxes, s); break;
-    case 10: launch_vector<T, 2, 2, 8, false, true>(ka, boxes, s); break;
-    case 12: launch_vector<T, 8, 4, 4, false, true, 2>(ka, boxes, s); break;
-    case 13: launch_vector<T, 4, 4, 4, false, true, 2>(ka, boxes, s); break;
-    case 15: launch_vector<T, 4, 8, 2, false, true, 2>(ka, boxes, s); break;
-    case 16: launch_vector<T, 8, 2, 4, false, true, 2>(ka, boxes, s); break;
-    case 17: launch_vector<T, 4, 4, 2, false, true, 4>(ka, boxes, s); break;
-    case 19: launch_vector<T, 4, 1, 2, false, true>(ka, boxes, s); break;
-    case 20: launch_vector<T, 4, 2, 4, false, false>(ka, boxes, s); break;
-#endif
+#define IGG_LAUNCH_S(BY, RY, VZ, PF, NT, BZ) launch_scalar<T, BY, RY, true>
+#define IGG_LAUNCH_V(BY, RY, VZ, PF, NT, BZ) launch_vector<T, BY, RY, VZ, PF, NT, BZ>
+#define IGG_ROW(C, I, NAME, K, ...) IGG_PASS_##C(case I: IGG_LAUNCH_##K(__VA_ARGS__)(ka, boxes, s); break;)
+#define IGG_PASS_CORE(...) __VA_ARGS__
+#define IGG_PASS_PROBES(...)
+    IGG_PLAIN_KERNELS(IGG_ROW)
+#undef IGG_PASS_CORE
+#undef IGG_PASS_PROBES
+#define IGG_PASS_CORE(...)
+#define IGG_PASS_PROBES(...) IGG_IF_PROBES(__VA_ARGS__)
+    IGG_PLAIN_KERNELS(IGG_ROW)
+#undef IGG_PASS_CORE
+#undef IGG_PASS_PROBES
+#undef IGG_ROW
+#undef IGG_LAUNCH_S
+#undef IGG_LAUNCH_V
     default: fail("diffusion3d: kernel variant ", v, " is not compiled in this build",
                   " (measurement-only variants: build.py --probes)");
   }
@@ -507,26 +433,8 @@ KArgs<T> make_args(const DiffusionArgs& a) {
 
 }  // namespace
 
-// Compiled variants of the default build: the autotune shortlist
-// (ops/stencil.py SHORTLIST: the variants that won an A/B on some box in rounds
-// 2-4), the plain tilings the fused/overlap paths and the restrict-form
-// variants fall back to for other boxes (0, 5, 9, 11, 14), the scalar fallback
-// (1) and the one-row slab kernel (18). The other tilings were measured in
-// rounds 1-4 and never won; they are built only with `build.py --probes`
-// (IGG_PROBES) for re-measurement.
-bool stencil_variant_compiled(int v) {
-#ifdef IGG_PROBES
-  return v >= 0 && v < NVARIANTS;
-#else
-  switch (v) {
-    case 0: case 1: case 2: case 5: case 9: case 11: case 14: case 18:
-    case 21: case 24: case 26: case 40: case 43: case 44:
-      return true;
-    default:
-      return false;
-  }
-#endif
-}
+// Build classes of the variants: igg/variants.hpp.
+bool stencil_variant_compiled(int v) { return v >= 0 && v < NVARIANTS && VARIANTS[v].compiled; }
 
 int64_t diffusion3d_target_blocks(const void* kernel, int block, int rounds) {
   const int saved = g_call_rounds;
@@ -544,9 +452,8 @@ const char* diffusion3d_variant_name(int v) {
 }
 int diffusion3d_variant_tile(int v) {
   if (v < 0 || v >= NVARIANTS) return 0;
-  if (v >= 21) v = HX_FALLBACK[v - 21];
-  const int bz = (v >= 12 && v <= 16) ? 2 : (v == 17 ? 4 : 1);
-  return 64 * VARIANTS[v].vz * bz;
+  const VariantRow& k = VARIANTS[VARIANTS[v].fallback];  // a 21+ variant reports its fallback's tile
+  return 64 * k.vz * k.bz;
 }
 
 void launch_diffusion3d(const DiffusionArgs& a, const std::vector<Box>& boxes, int variant,
@@ -563,16 +470,15 @@ void launch_diffusion3d(const DiffusionArgs& a, const std::vector<Box>& boxes, i
     for (int d = 0; d < 3; ++d)
       if (!b.empty() && (b.lo[d] < 1 || b.hi[d] > a.n[d] - 1))
         fail("diffusion3d: box outside the inner region [1, n-1) along dim ", d);
-  if (variant >= 21 && variant < NVARIANTS) {
-    const int tiling = HX_TILING[variant - 21];
+  if (const VariantRow& hx = VARIANTS[variant]; hx.tiling >= 0) {  // 21+: restrict form for the inner box
     const bool inner = boxes.size() == 1 && boxes[0].lo[0] == 1 && boxes[0].lo[1] == 1 && boxes[0].lo[2] == 1 &&
                        boxes[0].hi[0] == a.n[0] - 1 && boxes[0].hi[1] == a.n[1] - 1 && boxes[0].hi[2] == a.n[2] - 1;
-    const int vz = VARIANTS[variant].vz;
+    const int vz = restrict_tiling(hx.tiling)->vz;
     if (inner && a.n[2] % vz == 0 && a.n[2] >= 2 * vz) {
-      launch_diffusion3d_inner_hx(a, tiling, stream);
+      launch_diffusion3d_inner_hx(a, hx.tiling, stream);
       return;
     }
-    variant = HX_FALLBACK[variant - 21];
+    variant = hx.fallback;
   }
   if (a.elem_bytes == 8) dispatch<double>(make_args<double>(a), boxes, variant, stream);
   else if (a.elem_bytes == 4) dispatch<float>(make_args<float>(a), boxes, variant, stream);

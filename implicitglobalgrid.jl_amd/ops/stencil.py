@@ -34,7 +34,8 @@ def compiled_variants() -> list[int]:
     return [v for v in range(len(variants())) if native.diffusion3d_variant_compiled(v)]
 
 
-FUSED_VARIANTS = (0, 2, 9, 11, 14, 40, 41, 42, 44, 45, 48, 50)
+# Every fused variant of the catalogue (csrc/include/igg/variants.hpp), of both build classes.
+FUSED_VARIANTS = tuple(native.diffusion3d_fused_variants())
 
 
 def compiled_fused_variants() -> list[int]:

@@ -16,7 +16,7 @@ test still passes (compiling an unused path made every fused
 form 10-20 % slower). ``tests/test_kernel_resources.py`` compares the table
 against the checked-in baseline ``profiles/kernel_resources.json``.
 
-Usage: python tools/kernel_resources.py [--write BASELINE] [--markdown OUT]
+Usage: python tools/kernel_resources.py [--write BASELINE] [--markdown OUT] [--digests] [--tag TAG]
 """
 from __future__ import annotations
 
@@ -117,6 +117,16 @@ def table(objs: list[Path] | None = None) -> dict:
     return res
 
 
+def digests(objs: list[Path]) -> dict:
+    """{unit: sha256 of its unbundled gfx950 code object}: equal digests before
+    and after a change prove that it left the device code of a unit alone."""
+    import hashlib
+
+    with tempfile.TemporaryDirectory() as td:
+        return {obj.name.split(".hip.")[0]: hashlib.sha256(_code_object(obj, Path(td)).read_bytes()).hexdigest()
+                for obj in objs}
+
+
 def markdown(t: dict) -> str:
     lines = ["| unit | kernel | VGPR (arch+acc) | AGPR | SGPR | VGPR spill | SGPR spill | scratch B | LDS B | code B |",
              "|---|---|---|---|---|---|---|---|---|---|"]
@@ -131,11 +141,18 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--write", default=None, help="write the table as JSON (the baseline: profiles/kernel_resources.json)")
     ap.add_argument("--markdown", default=None, help="write the table as a markdown file")
+    ap.add_argument("--digests", action="store_true",
+                    help="print only the sha256 of each unit's gfx950 code object")
+    ap.add_argument("--tag", default="opt-fpc0", help="object tag of the build (build.py --probes: opt-probes-fpc0)")
     a = ap.parse_args()
-    objs = objects()
+    objs = objects(a.tag)
     if not objs:
         print("no HIP objects under build/native: run `python build.py` first", file=sys.stderr)
         return 1
+    if a.digests:
+        for unit, d in digests(objs).items():
+            print(f"{d}  {unit}")
+        return 0
     t = table(objs)
     if a.write:
         Path(a.write).write_text(json.dumps(t, indent=1, sort_keys=True) + "\n")
