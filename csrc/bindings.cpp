@@ -29,6 +29,7 @@
 #include "igg/reduce.hpp"
 #include "igg/sample.hpp"
 #include "igg/select.hpp"
+#include "igg/spread.hpp"
 #include "igg/stencil.hpp"
 #include "igg/topology.hpp"
 #include "igg/trace.hpp"
@@ -103,6 +104,72 @@ void sample_calls(const char* who, const std::vector<SampleDimTuple>& dims, cons
       for (int d = 0; d < 3; ++d) a.field[f].stride[d] = d < a.nd ? strides[d] : 0;
     }
     a.out = reinterpret_cast<uint64_t*>(out) + static_cast<int64_t>(f0) * out_fs;
+    run(a);
+  }
+}
+
+// spread_g's table as Python passes it: per dimension (E, periodic, m, [(g0, g1,
+// i0), ...] owned segments, [(i0, len, g0), ...] runs of the local range).
+using SpreadDimTuple =
+    std::tuple<int64_t, int, int64_t, std::vector<std::array<int64_t, 3>>, std::vector<std::array<int64_t, 3>>>;
+
+SpreadPlanArgs spread_plan_args(const char* who, const std::vector<SpreadDimTuple>& dims, int copies, uintptr_t points,
+                                int64_t ps0, int64_t ps1, int64_t npts) {
+  SpreadPlanArgs a;
+  a.nd = static_cast<int32_t>(dims.size());
+  if (a.nd < 1 || a.nd > 3) fail(who, ": fields must have 1 to 3 dimensions (got ", dims.size(), ")");
+  a.copies = copies;
+  for (int d = 0; d < a.nd; ++d) {
+    SpreadDim& S = a.dim[d];
+    SampleDim& D = S.own;
+    const auto& segs = std::get<3>(dims[d]);
+    const auto& runs = std::get<4>(dims[d]);
+    if (segs.size() > 2) fail(who, ": at most two owned segments per dimension");
+    if (runs.size() > SPREAD_MAX_RUNS) fail(who, ": at most ", SPREAD_MAX_RUNS, " runs per dimension");
+    auto narrow = [&](int64_t v) {
+      if (v < 0 || v > INT32_MAX) fail(who, ": ", v, " in the table of dimension ", d, " is negative or above 2^31 - 1");
+      return static_cast<int32_t>(v);
+    };
+    D.E = narrow(std::get<0>(dims[d])), D.per = std::get<1>(dims[d]) ? 1 : 0, D.m = narrow(std::get<2>(dims[d]));
+    D.nseg = static_cast<int32_t>(segs.size());
+    for (int s = 0; s < D.nseg; ++s)
+      D.g0[s] = narrow(segs[s][0]), D.g1[s] = narrow(segs[s][1]), D.i0[s] = narrow(segs[s][2]);
+    S.nrun = static_cast<int32_t>(runs.size());
+    for (int r = 0; r < S.nrun; ++r)
+      S.i0[r] = narrow(runs[r][0]), S.len[r] = narrow(runs[r][1]), S.g0[r] = narrow(runs[r][2]);
+  }
+  a.P = reinterpret_cast<const double*>(points), a.ps0 = ps0, a.ps1 = ps1, a.npts = npts;
+  return a;
+}
+
+// One SpreadArgs per SPREAD_MAX_FIELDS fields, each handed to `run`.
+template <typename Run>
+void spread_calls(const char* who, const std::vector<int64_t>& shape, const std::vector<SampleFieldTuple>& fields,
+                  int64_t ncells, uintptr_t cells, uintptr_t start, uintptr_t point, uintptr_t weight, uintptr_t values,
+                  int64_t v_fs, int64_t v_ps, uintptr_t row, int64_t nrows, int64_t row_stride, Run run) {
+  SpreadArgs a;
+  a.nd = static_cast<int32_t>(shape.size());
+  if (a.nd < 1 || a.nd > 3) fail(who, ": fields must have 1 to 3 dimensions (got ", shape.size(), ")");
+  if (fields.empty()) fail(who, ": at least one field is needed");
+  for (int d = 0; d < a.nd; ++d) {
+    if (shape[d] < 1 || shape[d] > INT32_MAX) fail(who, ": size ", shape[d], " in dimension ", d);
+    a.m[d] = shape[d];
+    a.numel *= shape[d];
+  }
+  a.ncells = ncells;
+  a.cells = reinterpret_cast<const int64_t*>(cells), a.start = reinterpret_cast<const int64_t*>(start);
+  a.point = reinterpret_cast<const int64_t*>(point), a.weight = reinterpret_cast<const double*>(weight);
+  a.v_fs = v_fs, a.v_ps = v_ps;
+  a.row = reinterpret_cast<const int64_t*>(row), a.nrows = nrows, a.row_stride = row_stride;
+  for (size_t f0 = 0; f0 < fields.size(); f0 += SPREAD_MAX_FIELDS) {
+    a.nf = static_cast<int32_t>(std::min<size_t>(fields.size() - f0, SPREAD_MAX_FIELDS));
+    for (int f = 0; f < a.nf; ++f) {
+      const auto& [ptr, strides] = fields[f0 + f];
+      if (static_cast<int>(strides.size()) != a.nd) fail(who, ": one stride per dimension of the field");
+      a.field[f].base = reinterpret_cast<void*>(ptr);
+      for (int d = 0; d < 3; ++d) a.field[f].stride[d] = d < a.nd ? strides[d] : 0;
+    }
+    a.V = reinterpret_cast<const double*>(values) + static_cast<int64_t>(f0) * v_fs;
     run(a);
   }
 }
@@ -793,6 +860,83 @@ PYBIND11_MODULE(_igg_native, m) {
         py::arg("npts"), py::arg("out"), py::arg("out_fs"), py::arg("me0"), py::arg("row") = 0, py::arg("nrows") = 0,
         py::arg("row_stride") = 0,
         "`sample` on host memory with the same expressions: the CPU path and the GPU tests' reference.");
+
+  // --- point spreading (parallel/spread_g.py)
+  m.attr("SPREAD_BLOCK") = SPREAD_BLOCK;
+  m.attr("SPREAD_MAX_BLOCKS") = SPREAD_MAX_BLOCKS;
+  m.attr("SPREAD_MAX_FIELDS") = SPREAD_MAX_FIELDS;
+  m.attr("SPREAD_MAX_RUNS") = SPREAD_MAX_RUNS;
+  m.def("spread_count",
+        [](const std::vector<SpreadDimTuple>& dims, int copies, uintptr_t points, int64_t ps0, int64_t ps1,
+           int64_t npts, uintptr_t count, uintptr_t stream, int max_blocks) {
+          SpreadPlanArgs a = spread_plan_args("spread_count", dims, copies, points, ps0, ps1, npts);
+          a.count = reinterpret_cast<int64_t*>(count);
+          spread_count(a, max_blocks, as_stream(stream));
+        },
+        py::arg("dims"), py::arg("copies"), py::arg("points"), py::arg("ps0"), py::arg("ps1"), py::arg("npts"),
+        py::arg("count"), py::arg("stream") = 0, py::arg("max_blocks") = 0,
+        "count[p] (int64, device) = the number of local cells that point p reaches. dims: per axis (E, periodic, m, "
+        "[(g0, g1, i0), ...] owned segments, [(i0, len, g0), ...] runs of the local range); copies: 0 every local "
+        "cell whose global index is a corner's (the runs), 1 the owner's two cells (the segments). An invalid point "
+        "and a corner with a zero factor reach nothing. max_blocks caps the grid (0: SPREAD_MAX_BLOCKS).");
+  m.def("spread_fill",
+        [](const std::vector<SpreadDimTuple>& dims, int copies, uintptr_t points, int64_t ps0, int64_t ps1,
+           int64_t npts, uintptr_t cum, int64_t nentries, uintptr_t key, uintptr_t point, uintptr_t weight,
+           uintptr_t stream, int max_blocks) {
+          SpreadPlanArgs a = spread_plan_args("spread_fill", dims, copies, points, ps0, ps1, npts);
+          a.cum = reinterpret_cast<const int64_t*>(cum), a.nentries = nentries;
+          a.key = reinterpret_cast<int64_t*>(key), a.point = reinterpret_cast<int64_t*>(point);
+          a.weight = reinterpret_cast<double*>(weight);
+          spread_fill(a, max_blocks, as_stream(stream));
+        },
+        py::arg("dims"), py::arg("copies"), py::arg("points"), py::arg("ps0"), py::arg("ps1"), py::arg("npts"),
+        py::arg("cum"), py::arg("nentries"), py::arg("key"), py::arg("point"), py::arg("weight"),
+        py::arg("stream") = 0, py::arg("max_blocks") = 0,
+        "The entries of every point, from cum[p - 1] on (cum: the inclusive running sum of spread_count's counts, "
+        "nentries its last value; nothing is written at or beyond nentries): key (the target cell's linear C-order "
+        "index in the field's shape), point and weight ((fx*fy)*fz in float64), the x corners outermost.");
+  m.def("host_spread_plan",
+        [](const std::vector<SpreadDimTuple>& dims, int copies, uintptr_t points, int64_t ps0, int64_t ps1,
+           int64_t npts) {
+          const SpreadPlan p =
+              host_spread_plan(spread_plan_args("host_spread_plan", dims, copies, points, ps0, ps1, npts));
+          auto raw = [](const void* d, size_t n) { return py::bytes(static_cast<const char*>(d), n); };
+          return py::make_tuple(raw(p.cells.data(), p.cells.size() * 8), raw(p.start.data(), p.start.size() * 8),
+                                raw(p.point.data(), p.point.size() * 8), raw(p.weight.data(), p.weight.size() * 8));
+        },
+        py::arg("dims"), py::arg("copies"), py::arg("points"), py::arg("ps0"), py::arg("ps1"), py::arg("npts"),
+        "The finished plan from host points, with the kernels' expressions and std::stable_sort: (cells, start, "
+        "point, weight) as the bytes of int64, int64, int64 and float64 arrays - the touched cells ascending, "
+        "ncells + 1 segment starts, and the entries sorted by (cell, point).");
+  m.def("spread_apply",
+        [](const std::vector<int64_t>& shape, const std::vector<SampleFieldTuple>& fields, int elem_size,
+           int64_t ncells, uintptr_t cells, uintptr_t start, uintptr_t point, uintptr_t weight, uintptr_t values,
+           int64_t v_fs, int64_t v_ps, uintptr_t row, int64_t nrows, int64_t row_stride, uintptr_t stream,
+           int max_blocks) {
+          spread_calls("spread_apply", shape, fields, ncells, cells, start, point, weight, values, v_fs, v_ps, row,
+                       nrows, row_stride,
+                       [&](const SpreadArgs& a) { spread_apply(a, elem_size, max_blocks, as_stream(stream)); });
+        },
+        py::arg("shape"), py::arg("fields"), py::arg("elem_size"), py::arg("ncells"), py::arg("cells"),
+        py::arg("start"), py::arg("point"), py::arg("weight"), py::arg("values"), py::arg("v_fs"), py::arg("v_ps"),
+        py::arg("row") = 0, py::arg("nrows") = 0, py::arg("row_stride") = 0, py::arg("stream") = 0,
+        py::arg("max_blocks") = 0,
+        "For every touched cell i of the plan and every field f (f32 / f64, device; (pointer, strides in elements)): "
+        "s = the fold in entry order, in float64, of weight[e] * values[f*v_fs + point[e]*v_ps] over e in [start[i], "
+        "start[i+1]); field[cells[i]] = T(double(field[cells[i]]) + s), cells[i] being the linear C-order index in "
+        "`shape`. With `row` (a device int64) the values move by *row * row_stride and nothing is done if *row >= "
+        "nrows. One launch per SPREAD_MAX_FIELDS fields, one lane per cell; max_blocks caps the grid.");
+  m.def("host_spread_apply",
+        [](const std::vector<int64_t>& shape, const std::vector<SampleFieldTuple>& fields, int elem_size,
+           int64_t ncells, uintptr_t cells, uintptr_t start, uintptr_t point, uintptr_t weight, uintptr_t values,
+           int64_t v_fs, int64_t v_ps, uintptr_t row, int64_t nrows, int64_t row_stride) {
+          spread_calls("host_spread_apply", shape, fields, ncells, cells, start, point, weight, values, v_fs, v_ps,
+                       row, nrows, row_stride, [&](const SpreadArgs& a) { host_spread_apply(a, elem_size); });
+        },
+        py::arg("shape"), py::arg("fields"), py::arg("elem_size"), py::arg("ncells"), py::arg("cells"),
+        py::arg("start"), py::arg("point"), py::arg("weight"), py::arg("values"), py::arg("v_fs"), py::arg("v_ps"),
+        py::arg("row") = 0, py::arg("nrows") = 0, py::arg("row_stride") = 0,
+        "`spread_apply` on host memory with the same expressions: the CPU path and the GPU tests' reference.");
 
   // --- transports
   py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

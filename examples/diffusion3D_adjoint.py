@@ -35,18 +35,6 @@ def local_copies(A, cell):
     return idx[0].view(-1, 1, 1), idx[1].view(1, -1, 1), idx[2].view(1, 1, -1)
 
 
-def owned_copy(A, cell):
-    """Local index of the global cell ``cell`` if this rank owns it, else None."""
-    at = []
-    for d, (a, b) in enumerate(igg.owned_ranges(A)):
-        ix = igg.indices_g(d, A)[a:b]
-        hit = (ix == cell[d]).nonzero().flatten()
-        if hit.numel() == 0:
-            return None
-        at.append(a + int(hit[0]))
-    return tuple(at)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=12)
@@ -67,9 +55,7 @@ def main():
 
     # backward: one adjoint sweep from the probe
     g = torch.zeros_like(T0)
-    at = owned_copy(g, probe)
-    if at is not None:
-        g[at] = 1.0
+    igg.spread_g(g, P, torch.ones(1, dtype=torch.float64), copies="owner")  # the transpose of the probe's sample_g
     grad = model.adjoint_run(a.nt, g)
     igg.accumulate_halo_(grad)  # overlap == 2 * halowidth: the owned cells now hold the global gradient
     total = float(igg.sum_g(grad))

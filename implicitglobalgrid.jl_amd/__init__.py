@@ -25,7 +25,11 @@ them (parallel/accumulate.py), with the differentiable exchange
 ``igg.autograd.update_halo`` built on it; and ``sample_g``, the fields' values
 at arbitrary points of the global grid, interpolated by the rank that owns
 each point's cell, with ``Recorder`` for time series of them
-(``sample_owner``, ``index_g``; parallel/sample_g.py); and the diffusion step
+(``sample_owner``, ``index_g``; parallel/sample_g.py), and its transpose
+``spread_g``, point values added into the fields without atomics, with
+``Source`` for a wavelet injected step by step (``spread_plan``,
+``spread_targets``; parallel/spread_g.py) and ``igg.autograd.sample_g`` built
+on it; and the diffusion step
 transposed (``ops.stencil.diffusion3d_adjoint_``), with the differentiable step
 ``igg.autograd.diffusion3d`` and the model's backward time loop
 ``Diffusion3D.adjoint_run``; and the acoustic step transposed
@@ -50,6 +54,7 @@ from .parallel.gather import gather, gather_, gather_async_  # noqa: F401
 from .parallel.gather_g import gather_g, indices_g, selection_shape_g  # noqa: F401
 from .parallel.scatter_g import scatter_g, scatter_pieces  # noqa: F401
 from .parallel.sample_g import Recorder, index_g, sample_g, sample_owner  # noqa: F401
+from .parallel.spread_g import Source, SpreadPlan, spread_g, spread_plan, spread_targets  # noqa: F401
 from .utils.tools import coords_g, nx_g, ny_g, nz_g, tic, toc, x_g, y_g, z_g  # noqa: F401
 from .utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .ops.reduce import (  # noqa: F401
@@ -77,4 +82,5 @@ __all__ = [
     "owned_ranges", "owned_view", "reduce_g", "sum_g", "max_g", "min_g", "maxabs_g", "dot_g", "maxabs_diff_g",
     "norm_g", "norm_diff_g", "mean_g", "project_g", "gather_g", "indices_g", "selection_shape_g",
     "scatter_g", "scatter_pieces", "accumulate_halo_", "autograd", "sample_g", "sample_owner", "index_g", "Recorder",
+    "spread_g", "spread_plan", "spread_targets", "SpreadPlan", "Source",
 ]

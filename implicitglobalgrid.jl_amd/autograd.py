@@ -19,6 +19,10 @@ is one differentiable step of the model on any number of ranks.
 of the adjoint kernel (``ops.stencil.acoustic2d_adjoint_``). The step is linear,
 so nothing is saved. ``update_halo(Vx2, Vy2)`` after it makes one differentiable
 step of that model on any number of ranks (``P2`` is never exchanged).
+
+``igg.autograd.sample_g(fields, P)`` is ``sample_g`` with a backward pass: its
+transpose ``spread_g(..., copies="owner")`` of the incoming gradient into
+zeros, so a loss on sampled values reaches the fields.
 """
 from __future__ import annotations
 
@@ -29,6 +33,8 @@ from torch.autograd.function import once_differentiable
 from .ops import stencil as _stencil
 from .parallel.accumulate import accumulate_halo_
 from .parallel.halo import update_halo_
+from .parallel.sample_g import sample_g as _sample_g
+from .parallel.spread_g import spread_g as _spread_g
 
 
 class _UpdateHalo(torch.autograd.Function):
@@ -132,3 +138,45 @@ def acoustic2d(P, Vx, Vy, *, dt: float, K: float, rho: float, dx: float, dy: flo
     ``None``. CPU and GPU tensors, float32 and float64; ``dt``, ``K``, ``rho``
     and the spacings are plain numbers (no gradient flows to them)."""
     return _Acoustic2D.apply(P, Vx, Vy, float(dt), float(K), float(rho), float(dx), float(dy))
+
+
+class _SampleG(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, single, *fields):
+        fs = tuple(A.detach() for A in fields)
+        ctx.P, ctx.single = P.detach(), single
+        ctx.like = [(A.shape, A.dtype, A.device, A.stride()) for A in fs]
+        return _sample_g(fs[0] if single else fs, ctx.P)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        g = gout.to(torch.float64).contiguous()
+        grads = []
+        for k, ((shape, dtype, device, stride), need) in enumerate(zip(ctx.like, ctx.needs_input_grad[2:])):
+            if not need:
+                grads.append(None)
+                continue
+            gA = torch.zeros(shape, dtype=dtype, device=device)
+            _spread_g(gA, ctx.P, g if ctx.single else g[k], copies="owner")
+            grads.append(gA)
+        return (None, None, *grads)
+
+
+def sample_g(fields, P):
+    """``sample_g(fields, P)`` (collective, identical on every rank);
+    differentiable in the fields, float32 or float64.
+
+    The gradient with respect to a field is ``spread_g`` of the incoming
+    gradient into zeros with ``copies="owner"``, in the field's dtype: the
+    exact transpose of the interpolation this rank did, so only the owner of a
+    point's cell receives, in the cells it read. There is no gradient for
+    ``P``. Convention: the incoming gradient is the same on every rank, as for
+    a loss that every rank computes from the (replicated) sampled values; the
+    per-rank gradients then add up over the ranks to the gradient of that one
+    loss. What belongs to another rank's copy of a cell is brought home by the
+    ``accumulate_halo_`` that ``adjoint_run`` and ``igg.autograd.update_halo``
+    already begin their backward pass with."""
+    single = isinstance(fields, torch.Tensor)
+    fs = (fields,) if single else tuple(fields)
+    return _SampleG.apply(P, single, *fs)

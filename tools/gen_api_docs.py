@@ -23,6 +23,7 @@ SECTIONS = [
     ("The global field: whole, sliced or coarsened", "igg", ["gather_g", "selection_shape_g", "indices_g"]),
     ("A global array into the fields", "igg", ["scatter_g", "scatter_pieces"]),
     ("Values at points of the global grid", "igg", ["sample_g", "index_g", "sample_owner", "Recorder"]),
+    ("Point values into the global grid", "igg", ["spread_g", "spread_plan", "SpreadPlan", "Source", "spread_targets"]),
     ("Global sizes and coordinates, timing", "igg",
      ["nx_g", "ny_g", "nz_g", "x_g", "y_g", "z_g", "coords_g", "tic", "toc"]),
     ("Global reductions", "igg",
@@ -35,7 +36,7 @@ SECTIONS = [
     ("Stencil ops", "igg.ops.stencil",
      ["diffusion3d_", "diffusion3d_adjoint_", "acoustic2d_adjoint_", "diffusion3d_reference", "time_variants",
       "autotune"]),
-    ("Differentiable operators", "igg.autograd", ["update_halo", "diffusion3d", "acoustic2d"]),
+    ("Differentiable operators", "igg.autograd", ["update_halo", "diffusion3d", "acoustic2d", "sample_g"]),
     ("Applications", "igg.models.diffusion3d", ["Diffusion3D"]),
     ("", "igg.models.acoustic2d", ["Acoustic2D"]),
     ("Field placement", "igg.utils.placement", ["candidate_count", "time_candidates", "placed"]),
